@@ -1,8 +1,8 @@
 """Collective bandwidth measurement: xGMI kernels vs RCCL at the sizes a DP job moves.
 
 North-star #2 of BASELINE.md ("xGMI custom allreduce bus bandwidth vs RCCL, 1 KB-256 MB",
-SURVEY.md §6) measured by the driver-run ``bench.py --gpus N`` itself, so the first real 8-GPU
-run records it next to the training throughput. The reference's counterpart is Horovod's NCCL
+SURVEY.md §6) measured by the driver-run ``bench.py --full --gpus N`` itself, so the first real
+8-GPU run records it next to the training throughput. The reference's counterpart is Horovod's NCCL
 allreduce inside the hvd image (charts/tf-horovod/README.md:66-69, values.yaml:14); this module
 times OUR two paths for the same operation:
 

@@ -8,8 +8,21 @@ north-star. We measure whole-job training throughput (samples/s, all ranks) with
 batch of 100 (weak scaling), full fp32 compute, every step complete (forward, loss, backward,
 gradient all-reduce when N>1, Adam update, device-side data gather + epoch reshuffles).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does only what the headline figure needs: set up, warm up, time ``--steps`` steps
+(``ms_per_step`` is the time of one of them), write ``--dump-outputs`` if asked, print the line.
+Everything else this file measures (ResNet-50, the collective table) runs under ``--full`` only.
+
+``--dump-outputs DIR`` writes what one step of the timed path computes as ``DIR/<name>.npy``
+(float32): the flat parameter and Adam moment buffers, the step's hidden activations, logits, loss
+and correct count (rank 0's replica at N > 1). Data, initial parameters, shuffle order and dropout
+masks are all seeded, but the logits are summed with float atomics and Adam amplifies their
+rounding from step to step, so the state after K steps is not the same on every run. The dumped
+step is therefore one more, untimed, call of the timed path after the timed ones, taken from the
+seeded start state: its inputs are bit-identical on every run and two builds can be compared
+array for array.
 
 ``--gpus N`` is honoured either way. Under torchrun (``WORLD_SIZE`` set) every rank is already a
 process. Without it and N > 1, this process becomes the launcher before it imports torch or touches
@@ -28,12 +41,12 @@ GPU, so the line says ``"emulated"`` and is NOT a scaling number.
 
 The MNIST steps run as replays of one hipGraph whose length divides the warmup, the timed step
 count and the epoch; ``config.exec`` reports how many timed steps were replayed vs run eagerly.
-The same line also carries ``resnet50_images_per_s`` (all ranks) / ``resnet50_ms_per_step``
-(ResNet-50 bs128 per GPU, bf16, whole training step in one hipGraph, data parallel over the
-sharded xGMI optimizer at N>1; ``--resnet 0`` skips it). At N>1 it also carries ``ccl``: xGMI vs
-RCCL time and bus bandwidth per collective and size, the xGMI self-test outcome per kernel and the
-protocol form in use (``--ccl 0`` skips it). A failed ResNet or collective run at N>1 is reported
-in the line (``failed``) and the process exits 3.
+With ``--full`` the same line also carries ``resnet50_images_per_s`` (all ranks) /
+``resnet50_ms_per_step`` (ResNet-50 bs128 per GPU, bf16, whole training step in one hipGraph, data
+parallel over the sharded xGMI optimizer at N>1; ``--resnet 0`` skips it). At N>1 ``--full`` also
+adds ``ccl``: xGMI vs RCCL time and bus bandwidth per collective and size, the xGMI self-test
+outcome per kernel and the protocol form in use (``--ccl 0`` skips it). A failed ResNet or
+collective run at N>1 is reported in the line (``failed``) and the process exits 3.
 
 Rank 0 prints ONE JSON line.
 """
@@ -57,6 +70,13 @@ def parse():
                          "scaling number")
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the ResNet-50 "
+                         "training benchmark (--resnet) and, at N>1, the collective table (--ccl)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, take one more step of the timed path from the "
+                         "seeded start state and write what it computed (parameters, Adam "
+                         "moments, activations and metrics) as DIR/<name>.npy")
     ap.add_argument("--impl", choices=["fused", "torch"], default="fused",
                     help="fused = arena_amd HIP kernels + hipGraph; torch = eager PyTorch baseline")
     ap.add_argument("--hidden", type=int, default=500)
@@ -71,14 +91,15 @@ def parse():
                          "(and the xGMI barrier flags) and abort on divergence; adds a host sync "
                          "per check. The replicas are always verified once after timing.")
     ap.add_argument("--resnet", type=int, default=1,
-                    help="1: also time ResNet-50 training (bs128/GPU, bf16, hipGraph; data "
-                         "parallel over all ranks at N>1) and report it as extra resnet50_* keys "
-                         "of the same JSON line")
+                    help="with --full, 1: also time ResNet-50 training (bs128/GPU, bf16, "
+                         "hipGraph; data parallel over all ranks at N>1) and report it as extra "
+                         "resnet50_* keys of the same JSON line")
     ap.add_argument("--resnet-steps", type=int, default=20)
     ap.add_argument("--resnet-batch", type=int, default=128)
     ap.add_argument("--ccl", type=int, default=1,
-                    help="N>1: also time allreduce 4 KB..256 MB, all-gather, broadcast and one "
-                         "ResNet-sized sharded-SGD bucket through xGMI and RCCL (key 'ccl')")
+                    help="with --full at N>1: also time allreduce 4 KB..256 MB, all-gather, "
+                         "broadcast and one ResNet-sized sharded-SGD bucket through xGMI and "
+                         "RCCL (key 'ccl')")
     ap.add_argument("--resnet-verify-every", type=int, default=10,
                     help="N>1: replica bit-identity check every K timed ResNet steps (untimed)")
     return ap.parse_args()
@@ -182,6 +203,69 @@ def bench_resnet50(dev, steps: int, batch: int, world: int = 1, verify_every: in
     return out
 
 
+_FUSED_STATE = ("P", "M", "V", "ctrA", "ctrB", "logits2", "rows", "loss_hist", "corr_hist", "perm")
+
+
+def snapshot_start(tr) -> dict:
+    """The trainer's seeded state before its first step (parameters, optimizer state, step
+    counters, epoch order and shuffle generator), for ``dump_outputs`` to return to."""
+    if hasattr(tr, "P"):   # fused trainer: flat device buffers
+        return {"tensors": {n: getattr(tr, n).clone() for n in _FUSED_STATE},
+                "steps_done": tr.steps_done, "rng": tr._gen.get_state()}
+    import copy            # eager PyTorch baseline
+    return {"model": copy.deepcopy(tr.model.state_dict()),
+            "opt": copy.deepcopy(tr.opt.state_dict()), "perm": tr.perm.clone(), "pos": tr.pos}
+
+
+def dump_outputs(tr, run, start: dict, out_dir: str, world: int, rank: int) -> None:
+    """Write what one step of the timed path computes from the seeded start state as
+    ``out_dir/<name>.npy`` (float32, a few MB in all, so nothing is sampled).
+
+    The state the timed steps themselves leave behind is not reproducible: the forward
+    accumulates its logits with float atomics whose order changes from run to run, and Adam
+    amplifies that rounding step after step until two runs of one build differ in the second
+    digit. So after timing the trainer is put back to ``start`` (``snapshot_start``, taken before
+    the warmup) and ``run(1)`` -- the call that was timed -- takes one more, untimed, step. Its
+    inputs are bit-identical on every run and its outputs differ by one step's rounding at most."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    if hasattr(tr, "P"):
+        for n, v in start["tensors"].items():
+            getattr(tr, n).copy_(v)
+        tr.steps_done = start["steps_done"]
+        tr._gen.set_state(start["rng"])
+    else:
+        tr.model.load_state_dict(start["model"])
+        tr.opt.load_state_dict(start["opt"])
+        tr.perm, tr.pos = start["perm"], start["pos"]
+        torch.manual_seed(tr.cfg.seed)   # the dropout masks come from the global generator
+    torch.cuda.synchronize()
+    if world > 1:   # every replica is back at the start before any rank reads a peer's buffers
+        import torch.distributed as dist
+        dist.barrier()
+    run(1)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    if rank != 0:
+        return
+    if hasattr(tr, "P"):   # flat buffers + the step's activations and metrics
+        n = tr.layout.total
+        last = int(tr.ctrA.item()) - 1          # index of the step just taken
+        slot = last % tr.cfg.hist_len
+        arrays = {"params": tr.P[:n], "adam_m": tr.M[:n], "adam_v": tr.V[:n],
+                  "hidden": tr.Hbuf, "logits": tr.logits2[last & 1],
+                  "loss": tr.loss_hist[slot:slot + 1], "correct": tr.corr_hist[slot:slot + 1]}
+    else:                  # the module's parameters and the step's loss
+        arrays = {"params": torch.cat([p.detach().reshape(-1) for p in tr.model.parameters()]),
+                  "loss": tr.losses[-1].reshape(1)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.detach().to(torch.float32).cpu().numpy())
+
+
 def launch_ranks(args, argv=None) -> int:
     """Launcher mode (``--gpus N > 1`` and no ``WORLD_SIZE``): start N ranks of this script and
     supervise them as a gang. Runs before torch is imported (no GPU call in this process)."""
@@ -257,6 +341,7 @@ def main():
         run = tr.train_steps
         mode = "eager-pytorch"
 
+    start = snapshot_start(tr) if args.dump_outputs else None
     run(args.warmup)
     torch.cuda.synchronize()
     if world > 1:
@@ -308,7 +393,10 @@ def main():
         extra["test_acc"] = round(ta, 5)
 
     failed = []
-    if args.resnet and args.impl == "fused":
+    if args.dump_outputs:
+        dump_outputs(tr, run, start, args.dump_outputs, world, rank)
+
+    if args.full and args.resnet and args.impl == "fused":
         del tr
         torch.cuda.empty_cache()
         try:
@@ -318,7 +406,7 @@ def main():
             print(f"[bench] ResNet-50 failed: {e!r}", file=sys.stderr)
             extra["resnet50_error"] = repr(e)[:300]
             failed.append("resnet50")
-    if world > 1 and args.ccl:
+    if args.full and world > 1 and args.ccl:
         # north-star #2: xGMI vs RCCL collective bandwidth on this node
         from arena_amd.parallel import cclbench
         torch.cuda.empty_cache()
