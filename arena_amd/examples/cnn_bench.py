@@ -69,20 +69,49 @@ def parse(argv=None):
                     help="data parallel: every K steps check that all replicas hold bit-identical "
                          "parameters (and that no xGMI barrier timed out); abort if not. The "
                          "replicas are always verified once at the end")
+    ap.add_argument("--label_smoothing", type=float, default=0.0,
+                    help="label smoothing of the loss (tf_cnn_benchmarks' flag; 0.1 is the usual "
+                         "ResNet-50 recipe)")
+    ap.add_argument("--print_training_accuracy", action="store_true",
+                    help="top_1_accuracy / top_5_accuracy on every display line, counted on the "
+                         "device by the loss kernels (no extra pass, no per-step host read)")
+    ap.add_argument("--eval", action="store_true",
+                    help="forward-only run (model.eval(), no optimizer): images/sec lines, then "
+                         "tf_cnn_benchmarks' 'Accuracy @ 1 = ... Accuracy @ 5 = ...' line")
     ap.add_argument("--json", action="store_true", help="print one JSON summary line at the end")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not 0.0 <= args.label_smoothing <= 1.0:
+        ap.error("--label_smoothing must lie in [0, 1]")
+    return args
 
 
-def build(args, dev, world):
-    """Model, optimizer (wrapped for DP) and one synthetic batch, ready to step."""
+def build_model(args, dev):
+    """The model, with rank 0's initial weights on every rank."""
     from ..models.resnet import resnet
     from ..parallel import hvd
     torch.manual_seed(1234)
     model = resnet(args.model, num_classes=args.num_classes, width=args.width).to(dev)
-    nhwc = dev.type == "cuda" and args.data_format == "NHWC"
-    if nhwc:
+    if dev.type == "cuda" and args.data_format == "NHWC":
         model = model.to(memory_format=torch.channels_last)
     hvd.broadcast_parameters(model.state_dict(), root_rank=0)
+    return model
+
+
+def synthetic_batch(args, dev):
+    """One synthetic batch (per-rank seed)."""
+    from ..parallel import hvd
+    g = torch.Generator(device=dev).manual_seed(hvd.rank())
+    x = torch.randn(args.batch_size, 3, args.image_size, args.image_size, device=dev, generator=g)
+    if dev.type == "cuda" and args.data_format == "NHWC":
+        x = x.contiguous(memory_format=torch.channels_last)
+    y = torch.randint(0, args.num_classes, (args.batch_size,), device=dev, generator=g)
+    return x, y
+
+
+def build(args, dev, world):
+    """Model, optimizer (wrapped for DP) and one synthetic batch, ready to step."""
+    from ..parallel import hvd
+    model = build_model(args, dev)
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         (no_decay if p.ndim <= 1 else decay).append(p)   # no decay on BN / bias
@@ -128,11 +157,7 @@ def build(args, dev, world):
     if world > 1 and not master:
         opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
                                        bucket_mb=args.bucket_mb, comm=args.comm)
-    g = torch.Generator(device=dev).manual_seed(hvd.rank())
-    x = torch.randn(args.batch_size, 3, args.image_size, args.image_size, device=dev, generator=g)
-    if nhwc:
-        x = x.contiguous(memory_format=torch.channels_last)
-    y = torch.randint(0, args.num_classes, (args.batch_size,), device=dev, generator=g)
+    x, y = synthetic_batch(args, dev)
     return model, opt, x, y
 
 
@@ -156,13 +181,18 @@ def comms_of(opt) -> list:
     return [getattr(opt, "xgmi", None)]
 
 
-def train_step(model, opt, x, y, amp_dtype, zero_grad=True):
+def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None):
+    """One training step. ``head``: keyword arguments for ``ops.pool.cross_entropy``
+    (``label_smoothing``, ``stats``, ``ignore_index``); None is the plain mean loss."""
     with torch.autocast(device_type=x.device.type, dtype=amp_dtype, enabled=amp_dtype is not None,
                         cache_enabled=False):
         logits = model(x)
     # (outside autocast: the fused loss takes the bf16 logits as they are and sums in fp32, as
     # autocast's fp32 cross_entropy does after its upcast copy)
-    if x.is_cuda:
+    if head is not None:
+        from ..ops.pool import cross_entropy
+        loss = cross_entropy(logits, y, **head)
+    elif x.is_cuda:
         from ..ops.pool import cross_entropy
         loss = cross_entropy(logits, y)
     else:
@@ -177,14 +207,14 @@ def train_step(model, opt, x, y, amp_dtype, zero_grad=True):
     return loss.detach()
 
 
-def capture_step(model, opt, x, y, amp_dtype):
+def capture_step(model, opt, x, y, amp_dtype, *, head=None):
     """The whole step as one hipGraph: ~800 kernels per ResNet-50 step replay without host
     launches or inter-kernel gaps. Gradients are None at capture, so the captured backward writes
     (not accumulates) them, and every replay reuses the same memory (static x, y)."""
     opt.zero_grad(set_to_none=True)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, capture_error_mode="thread_local"):
-        loss = train_step(model, opt, x, y, amp_dtype, zero_grad=False)
+        loss = train_step(model, opt, x, y, amp_dtype, zero_grad=False, head=head)
     return g, loss
 
 
@@ -206,7 +236,15 @@ def main(argv=None) -> int:
             raise SystemExit("--async_wgrad on is single-rank only (DP hooks read gradients "
                              "as soon as autograd produces them)")
         conv.set_async_wgrad(args.async_wgrad == "on")
+    if args.eval:
+        return evaluate(args, dev, world, rank, amp)
     model, opt, x, y = build(args, dev, world)
+    head = stats = None
+    if args.label_smoothing != 0.0 or args.print_training_accuracy:
+        # [kept, top-1, top-5, invalid labels], added to by the loss kernels on the device (so a
+        # replayed graph keeps counting); allocated before warm-up and capture
+        stats = torch.zeros(4, dtype=torch.int64, device=dev)
+        head = {"label_smoothing": args.label_smoothing, "stats": stats}
 
     def sync():
         if dev.type == "cuda":
@@ -219,7 +257,7 @@ def main(argv=None) -> int:
               f"{comm_name(opt)}", flush=True)
     for i in range(args.num_warmup_batches):
         t = time.perf_counter()
-        train_step(model, opt, x, y, amp)
+        train_step(model, opt, x, y, amp, head=head)
         sync()
         if rank == 0:   # the first steps include MIOpen's solver search: show progress
             print(f"warmup {i + 1}/{args.num_warmup_batches}: {time.perf_counter() - t:.2f} s",
@@ -232,7 +270,7 @@ def main(argv=None) -> int:
         # exactly where eager mode issues them; all ranks replay the same collective sequence.
         ok = True
         try:
-            graph, g_loss = capture_step(model, opt, x, y, amp)
+            graph, g_loss = capture_step(model, opt, x, y, amp, head=head)
         except RuntimeError as e:  # capture refused by a library call: run eagerly
             graph, ok = None, False
             print(f"[rank {rank}] hipGraph capture failed, running eagerly: {e}", flush=True)
@@ -254,6 +292,7 @@ def main(argv=None) -> int:
         from ..parallel.verify import ReplicaCheck
         check = ReplicaCheck(args.verify_every, lambda: list(model.parameters()),
                              comms=comms_of(opt))
+    seen0 = seen = stats.tolist() if stats is not None else None   # warm-up's counts excluded
     t0 = t_last = time.perf_counter()
     loss = None
     for i in range(1, args.num_batches + 1):
@@ -261,7 +300,7 @@ def main(argv=None) -> int:
             graph.replay()
             loss = g_loss
         else:
-            loss = train_step(model, opt, x, y, amp)
+            loss = train_step(model, opt, x, y, amp, head=head)
         heartbeat.beat(i)
         if check is not None:
             check.maybe(i)
@@ -269,9 +308,16 @@ def main(argv=None) -> int:
             sync()
             now = time.perf_counter()
             n = args.display_every if i % args.display_every == 0 else i % args.display_every
+            acc = ""
+            if args.print_training_accuracy:   # one read per display line, at its sync
+                cur = stats.tolist()
+                kept = max(cur[0] - seen[0], 1)
+                acc = (f"  top_1_accuracy: {(cur[1] - seen[1]) / kept:.4f}"
+                       f"  top_5_accuracy: {(cur[2] - seen[2]) / kept:.4f}")
+                seen = cur
             if rank == 0:
                 ips = n * args.batch_size / (now - t_last)
-                print(f"{i}\timages/sec: {ips:.1f} (per device)  loss {float(loss):.3f}",
+                print(f"{i}\timages/sec: {ips:.1f} (per device)  loss {float(loss):.3f}{acc}",
                       flush=True)
             t_last = now
     sync()
@@ -283,24 +329,126 @@ def main(argv=None) -> int:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     total = args.num_batches * args.batch_size * world / elapsed
+    counts = None
+    if stats is not None:
+        counts = global_counts(stats, seen0, world)
     if rank == 0:
         print("-" * 64)
         print(f"total images/sec: {total:.2f}", flush=True)
         print("-" * 64)
         if args.json:
-            print(json.dumps({"model": args.model, "images_per_s": round(total, 2),
-                              "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
-                              "batch_per_device": args.batch_size, "devices": world,
-                              "dtype": args.dtype, "comm": comm_name(opt),
-                              "exec": "hipgraph" if graph is not None else "eager",
-                              "final_loss": round(float(loss), 4)}), flush=True)
+            res = {"model": args.model, "images_per_s": round(total, 2),
+                   "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
+                   "batch_per_device": args.batch_size, "devices": world,
+                   "dtype": args.dtype, "comm": comm_name(opt),
+                   "exec": "hipgraph" if graph is not None else "eager",
+                   "final_loss": round(float(loss), 4)}
+            if counts is not None:
+                res.update(accuracy_fields(counts))
+            print(json.dumps(res), flush=True)
     if rank == 0 and os.environ.get("ARENA_CONV_LOG"):
         from ..ops import conv
         for key, plan in conv.plans().items():
             print(f"conv {key[0]} w{key[1]} s{key[2]} p{key[3]}: fwd={plan.fwd} bwd={plan.bwd} "
                   f"bwd_bn={plan.bwd_bn} wgrad={plan.wgrad} {plan.times}", file=sys.stderr)
     hvd.shutdown()
-    return 0
+    return invalid_labels_error(counts, rank)
+
+
+def global_counts(stats, base, world) -> list:
+    """[kept, top-1, top-5, invalid] since ``base`` (a host copy of ``stats``), summed over ranks."""
+    t = stats - torch.tensor(base, dtype=stats.dtype, device=stats.device)
+    if world > 1:
+        torch.distributed.all_reduce(t)
+    return t.tolist()
+
+
+def accuracy_fields(counts) -> dict:
+    kept = max(counts[0], 1)
+    return {"top_1_accuracy": round(counts[1] / kept, 4),
+            "top_5_accuracy": round(counts[2] / kept, 4), "invalid_labels": counts[3]}
+
+
+def invalid_labels_error(counts, rank) -> int:
+    """Exit status: labels outside [0, classes) were dropped from the loss, which is an error in
+    the input pipeline, not something to average over."""
+    if counts is None or counts[3] == 0:
+        return 0
+    if rank == 0:
+        print(f"error: {counts[3]} labels outside [0, num_classes) were dropped from the loss",
+              file=sys.stderr, flush=True)
+    return 1
+
+
+def evaluate(args, dev, world, rank, amp) -> int:
+    """``--eval``: forward-only passes over the synthetic batch in eval mode (BatchNorm on its
+    running statistics), eager, with training's warm-up and display cadence; ends with
+    tf_cnn_benchmarks' accuracy line, counted over all ranks."""
+    from ..ops.pool import cross_entropy
+    from ..parallel import hvd
+    model = build_model(args, dev).eval()
+    x, y = synthetic_batch(args, dev)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+
+    def step():
+        with torch.no_grad():
+            with torch.autocast(device_type=dev.type, dtype=amp, enabled=amp is not None,
+                                cache_enabled=False):
+                logits = model(x)
+            return cross_entropy(logits, y, label_smoothing=args.label_smoothing, stats=stats)
+
+    if rank == 0:
+        print(f"Model: {args.model}  Batch size: {args.batch_size} per device, "
+              f"{args.batch_size * world} global  Devices: {world} x {dev.type}  "
+              f"Data: synthetic  dtype: {args.dtype}  mode: eval", flush=True)
+    for i in range(args.num_warmup_batches):
+        step()
+    sync()
+    if world > 1:
+        torch.distributed.barrier()
+    base = stats.tolist()
+    t0 = t_last = time.perf_counter()
+    loss = None
+    for i in range(1, args.num_batches + 1):
+        loss = step()
+        heartbeat.beat(i)
+        if i % args.display_every == 0 or i == args.num_batches:
+            sync()
+            now = time.perf_counter()
+            n = args.display_every if i % args.display_every == 0 else i % args.display_every
+            if rank == 0:
+                ips = n * args.batch_size / (now - t_last)
+                print(f"{i}\timages/sec: {ips:.1f} (per device)  loss {float(loss):.3f}",
+                      flush=True)
+            t_last = now
+    sync()
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    total = args.num_batches * args.batch_size * world / elapsed
+    counts = global_counts(stats, base, world)
+    if rank == 0:
+        kept = max(counts[0], 1)
+        print("-" * 64)
+        print(f"total images/sec: {total:.2f}")
+        print("-" * 64)
+        print("Accuracy @ 1 = %.4f Accuracy @ 5 = %.4f [%d examples]"
+              % (counts[1] / kept, counts[2] / kept, counts[0]), flush=True)
+        if args.json:
+            res = {"model": args.model, "images_per_s": round(total, 2),
+                   "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
+                   "batch_per_device": args.batch_size, "devices": world, "dtype": args.dtype,
+                   "exec": "eval", "final_loss": round(float(loss), 4)}
+            res.update(accuracy_fields(counts))
+            print(json.dumps(res), flush=True)
+    hvd.shutdown()
+    return invalid_labels_error(counts, rank)
 
 
 if __name__ == "__main__":

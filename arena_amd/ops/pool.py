@@ -5,6 +5,10 @@ channels_last bf16/fp32 input whose C is a multiple of 8 it runs the HIP kernels
 stores a uint8 window position per output element, and the backward gathers each input's
 gradient from the windows that picked it (no atomics, no zero-fill). Anything else, including
 CPU tensors, runs ``F.max_pool2d``, which is also the numerics reference.
+
+The same file holds the ResNet head's other kernels: ``global_avg_pool`` (one-pass channels_last
+backward) and ``cross_entropy``, the fused softmax cross-entropy (mean) with optional
+``ignore_index``, label smoothing, label range checks and on-device top-1 / top-5 counts.
 """
 from __future__ import annotations
 
@@ -104,12 +108,89 @@ class _SoftmaxXentFn(torch.autograd.Function):
         return _ext.load().xent_bwd(logits, labels, lse, g.float().reshape(1)), None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    """``F.cross_entropy(logits, labels)`` (mean reduction, fp32 result, no ignore_index / label
-    smoothing) on the GPU through the ``pool_kernels.hip`` xent kernels: forward per-row loss +
-    log-sum-exp (one wave per row) and their mean, backward one elementwise pass in the logits'
-    dtype. Anything else runs the stock op."""
-    if (logits.is_cuda and logits.dim() == 2 and labels.dim() == 1
-            and labels.dtype == torch.int64 and logits.dtype in (torch.bfloat16, torch.float32)):
-        return _SoftmaxXentFn.apply(logits.contiguous(), labels.contiguous())
-    return F.cross_entropy(logits.float(), labels)
+class _SoftmaxXentExFn(torch.autograd.Function):
+    """The head with ignore_index / label smoothing / label checks / top-k counts: forward,
+    finalize and backward kernels; 1 / kept stays on the device (no host read: capturable)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, eps, stats):
+        loss, lse, meta, inv = _ext.load().xent_ex_fwd(
+            logits, labels, ignore_index is not None,
+            0 if ignore_index is None else int(ignore_index), eps, stats)
+        ctx.save_for_backward(logits, labels, lse, meta, inv)
+        ctx.eps = eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, labels, lse, meta, inv = ctx.saved_tensors
+        dx = _ext.load().xent_ex_bwd(logits, labels, lse, meta, inv, g.float().reshape(1), ctx.eps)
+        return dx, None, None, None, None
+
+
+def _cross_entropy_torch(logits, labels, ignore_index, eps, stats):
+    """``cross_entropy``'s extended semantics in stock torch ops (the numerics reference of the
+    kernels, and the path of CPU tensors and other dtypes)."""
+    x = logits.float()
+    classes = x.shape[1]
+    valid = (labels >= 0) & (labels < classes)
+    ignored = (labels == ignore_index) if ignore_index is not None else torch.zeros_like(valid)
+    keep = valid & ~ignored
+    # invalid labels are dropped like ignored ones (F.cross_entropy would raise on them)
+    loss = F.cross_entropy(x, torch.where(keep, labels, torch.full_like(labels, -100)),
+                           ignore_index=-100, label_smoothing=eps)
+    if stats is not None:
+        with torch.no_grad():
+            xd = x.detach()
+            xt = xd.gather(1, labels.clamp(0, classes - 1)[:, None])
+            rank = (xd > xt).sum(1)   # tf.nn.in_top_k's rule: ties at the boundary count as in
+            stats.add_(torch.stack([keep.sum(), (keep & (rank < 1)).sum(),
+                                    (keep & (rank < 5)).sum(), (~valid & ~ignored).sum()]))
+    return loss
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, *, ignore_index: int | None = None,
+                  label_smoothing: float = 0.0, stats: torch.Tensor | None = None) -> torch.Tensor:
+    """``F.cross_entropy(logits, labels)`` (mean reduction, fp32 result) on the GPU through the
+    ``pool_kernels.hip`` xent kernels: forward per-row loss + log-sum-exp (one wave per row), their
+    mean, and a backward of one elementwise pass in the logits' dtype.
+
+    With the defaults (``ignore_index=None``, ``label_smoothing=0.0``, ``stats=None``) this is the
+    original head: no label checks (an out-of-range label is clamped), mean over all rows. Any
+    other value takes the extended kernels (three launches too, no host read, capturable):
+
+    * ``ignore_index``: any int (it may be a valid class); such rows are dropped from the mean and
+      get an exactly zero gradient. All rows dropped: the loss is NaN and the gradient zero, as
+      torch.
+    * labels outside ``[0, classes)`` that are not ``ignore_index`` are *invalid*: dropped like
+      ignored rows, and counted in ``stats[3]`` (the stock op would raise).
+    * ``label_smoothing`` in ``[0, 1]``: ``(1-e)(lse - x_t) + e(lse - mean_c x_c)`` per row.
+    * ``stats``: an int64 ``[4]`` tensor on the logits' device that each call adds
+      ``[kept rows, top-1 correct, top-5 correct, invalid labels]`` to. A row is top-k correct iff
+      fewer than k classes have a logit strictly greater than the label's (``tf.nn.in_top_k``'s
+      rule: ties at the boundary count as correct), compared in fp32 on the stored logits.
+
+    Anything the kernels do not take (CPU tensors, other dtypes) runs the same semantics in stock
+    torch ops."""
+    if ignore_index is None and label_smoothing == 0.0 and stats is None:
+        if (logits.is_cuda and logits.dim() == 2 and labels.dim() == 1
+                and labels.dtype == torch.int64
+                and logits.dtype in (torch.bfloat16, torch.float32)):
+            return _SoftmaxXentFn.apply(logits.contiguous(), labels.contiguous())
+        return F.cross_entropy(logits.float(), labels)
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must lie in [0, 1], got {label_smoothing}")
+    if ignore_index is not None:
+        ignore_index = int(ignore_index)
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError("cross_entropy: logits [rows, classes] and labels [rows]")
+    if stats is not None and (stats.dtype != torch.int64 or stats.shape != (4,)
+                              or stats.device != logits.device):
+        raise ValueError("stats must be an int64 [4] tensor on the logits' device")
+    if (logits.is_cuda and labels.is_cuda and labels.dtype == torch.int64
+            and logits.dtype in (torch.bfloat16, torch.float32) and logits.numel() > 0
+            and (stats is None or stats.is_contiguous())):
+        return _SoftmaxXentExFn.apply(logits.contiguous(), labels.contiguous(), ignore_index, eps,
+                                      stats)
+    return _cross_entropy_torch(logits, labels, ignore_index, eps, stats)

@@ -114,6 +114,12 @@ hipError_t arena_xent_fwd(int, const void*, const long long*, float*, float*, in
 hipError_t arena_gap_bwd(int, const void*, void*, int, int, int, float, hipStream_t);
 hipError_t arena_xent_bwd(int, const void*, const long long*, const float*, const float*, void*,
                           int, int, hipStream_t);
+hipError_t arena_xent_ex_fwd(int, const void*, const long long*, float*, float*, int*, int, int,
+                             int, long long, float, hipStream_t);
+hipError_t arena_xent_ex_finalize(const float*, const int*, int, float*, float*, long long*,
+                                  hipStream_t);
+hipError_t arena_xent_ex_bwd(int, const void*, const long long*, const float*, const int*,
+                             const float*, const float*, void*, int, int, float, hipStream_t);
 hipError_t arena_bn_fwd(int, const void*, const void*, void*, uint8_t*, long long, int, int, int,
                         float*, int, long long, double*, unsigned*, ArenaBNStats, double*, int,
                         double*, int, hipStream_t);
@@ -1806,6 +1812,66 @@ Tensor xent_bwd(Tensor x, Tensor y, Tensor lse, Tensor gout) {
   return dx;
 }
 
+// The same head with ignore_index / label smoothing / label checks / top-k counts: forward +
+// finalize -> (loss, per-row log-sum-exp, per-row rank-or-dropped code, 1 / kept). ``stats`` (int64 [4]:
+// kept, top-1, top-5, invalid labels) is added to on the device.
+std::vector<Tensor> xent_ex_fwd(Tensor x, Tensor y, bool has_ignore, int64_t ignore_index,
+                                double eps, OptT stats) {
+  xent_check(x, y);
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "xent_ex: label_smoothing must lie in [0, 1]");
+  long long* pstats = nullptr;
+  if (stats.has_value() && stats->defined()) {
+    TORCH_CHECK(stats->is_cuda() && stats->device() == x.device() &&
+                    stats->scalar_type() == torch::kInt64 && stats->dim() == 1 &&
+                    stats->size(0) == 4 && stats->is_contiguous(),
+                "xent_ex: stats must be an int64 [4] GPU tensor on the logits' device");
+    pstats = reinterpret_cast<long long*>(stats->data_ptr<int64_t>());
+  }
+  const int64_t rows = x.size(0);
+  Tensor fbuf = torch::empty({2, rows}, x.options().dtype(torch::kFloat32));
+  // per row: the label's rank (>= 0) if the row is kept, negative if it was dropped
+  Tensor meta = torch::empty({rows}, x.options().dtype(torch::kInt32));
+  Tensor lse = fbuf[0], rowloss = fbuf[1];
+  Tensor loss = torch::empty({}, x.options().dtype(torch::kFloat32));
+  Tensor inv = torch::empty({1}, x.options().dtype(torch::kFloat32));
+  check_hip(arena_xent_ex_fwd(x.scalar_type() == torch::kBFloat16 ? 1 : 0, x.data_ptr(),
+                              reinterpret_cast<const long long*>(y.data_ptr<int64_t>()),
+                              rowloss.data_ptr<float>(), lse.data_ptr<float>(),
+                              meta.data_ptr<int>(), (int)rows, (int)x.size(1),
+                              has_ignore ? 1 : 0, (long long)ignore_index, (float)eps,
+                              cur_stream()),
+            "xent_ex_fwd");
+  check_hip(arena_xent_ex_finalize(rowloss.data_ptr<float>(), meta.data_ptr<int>(), (int)rows,
+                                   loss.data_ptr<float>(), inv.data_ptr<float>(), pstats,
+                                   cur_stream()),
+            "xent_ex_finalize");
+  return {loss, lse, meta, inv};
+}
+
+Tensor xent_ex_bwd(Tensor x, Tensor y, Tensor lse, Tensor meta, Tensor inv, Tensor gout,
+                   double eps) {
+  xent_check(x, y);
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat32 && lse.numel() == x.size(0) &&
+                  lse.is_contiguous() && gout.is_cuda() &&
+                  gout.scalar_type() == torch::kFloat32 && gout.numel() == 1,
+              "xent_ex_bwd: lse fp32 [rows], grad fp32 scalar");
+  TORCH_CHECK(meta.is_cuda() && meta.scalar_type() == torch::kInt32 &&
+                  meta.numel() == x.size(0) && meta.is_contiguous() && inv.is_cuda() &&
+                  inv.scalar_type() == torch::kFloat32 && inv.numel() == 1,
+              "xent_ex_bwd: meta int32 [rows], 1/kept fp32 scalar");
+  TORCH_CHECK(lse.device() == x.device() && meta.device() == x.device() &&
+                  inv.device() == x.device() && gout.device() == x.device(),
+              "xent_ex_bwd: tensors on one device");
+  Tensor dx = torch::empty_like(x);
+  check_hip(arena_xent_ex_bwd(x.scalar_type() == torch::kBFloat16 ? 1 : 0, x.data_ptr(),
+                              reinterpret_cast<const long long*>(y.data_ptr<int64_t>()),
+                              lse.data_ptr<float>(), meta.data_ptr<int>(), inv.data_ptr<float>(),
+                              gout.contiguous().data_ptr<float>(), dx.data_ptr(), (int)x.size(0),
+                              (int)x.size(1), (float)eps, cur_stream()),
+            "xent_ex_bwd");
+  return dx;
+}
+
 // Global-average-pool backward: g [N, C] -> channels_last [N, C, H, W] filled with g / (H W).
 Tensor gap_bwd(Tensor g, int64_t H, int64_t W) {
   TORCH_CHECK(g.is_cuda() && g.dim() == 2 && g.is_contiguous() &&
@@ -2033,6 +2099,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("xent_fwd", &xent_fwd);
   m.def("xent_bwd", &xent_bwd);
+  m.def("xent_ex_fwd", &xent_ex_fwd);
+  m.def("xent_ex_bwd", &xent_ex_bwd);
   m.def("gap_bwd", &gap_bwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("bn_set_fin_max_blocks", [](int64_t p) { arena_bn_set_fin_max_blocks((int)p); });

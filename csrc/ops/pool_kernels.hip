@@ -365,6 +365,228 @@ hipError_t arena_xent_bwd(int dtype, const void* x, const long long* y, const fl
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------
+// The same head with ignore_index, label smoothing, label checks and top-k counts (the legacy
+// kernels above stay as they are: the default path of ops.pool.cross_entropy). Three launches:
+//   forward   as above (one wave per row, four rows per block, register form up to 1024 classes),
+//             plus per row: keep = label != ignore_index && 0 <= label < classes (the label is
+//             range-checked before any index is formed from it; a label that is neither ignored
+//             nor in range is "invalid": dropped like an ignored row, and counted), the smoothed
+//             loss (1-e)(lse - x_t) + e(lse - mean_c x_c) with sum(x_c - m) accumulated for
+//             stability, and the label's rank = #{c : x_c > x_t} on the stored values (fp32
+//             compare), so "rank < k" is tf.nn.in_top_k's rule: ties at the boundary count as in;
+//   finalize  one block: loss = sum(rowloss) / kept (NaN when nothing is kept, as torch), 1 / kept
+//             (0 when nothing is kept) for the backward, and [kept, top1, top5, invalid] added to
+//             the caller's int64 counters by one thread (plain read-modify-write: launches on one
+//             stream are ordered). Fixed summation order, no float atomics: bit-reproducible;
+//   backward  dx = g * keep * (p - (1-e) onehot - e / classes) / kept, dropped rows exact zeros.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// meta[row]: the label's rank (>= 0) for a kept row, else why the row was dropped
+constexpr int kXentIgnored = -1, kXentInvalid = -2;
+
+template <typename T, int NPL>
+__global__ __launch_bounds__(256) void xent_ex_fwd_kernel(
+    const T* __restrict__ x, const long long* __restrict__ y, float* __restrict__ rowloss,
+    float* __restrict__ lse, int* __restrict__ meta, int rows, int classes, int has_ignore,
+    long long ignore_index, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const T* xr = x + (long long)r * classes;
+  // The label first (wave-uniform address): x_t's load depends on it, and issued here it is in
+  // flight together with the row's loads instead of after them.
+  const long long t = y[r];
+  const bool ignored = has_ignore && t == ignore_index;
+  const bool kept = !ignored && t >= 0 && t < classes;
+  // x_t through a checked index: the label itself for a kept row, else column 0 (value unused)
+  const int ti = kept ? (int)t : 0;
+  float m = -INFINITY, s = 0.f, d = 0.f, xt;
+  int above = 0;
+  if constexpr (NPL > 0) {
+    // Columns past the row's end load its last element (index clamped, value replaced): loads
+    // under a per-lane condition each become a branch with its own wait, one latency after the
+    // other; unconditional ones are all in flight at once.
+    float v[NPL];
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      const int c = lane + 64 * j;
+      v[j] = xent_ld(xr, c < classes ? c : classes - 1);
+    }
+    xt = xent_ld(xr, ti);
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) v[j] = lane + 64 * j < classes ? v[j] : -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) m = fmaxf(m, v[j]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      const bool in = lane + 64 * j < classes;
+      s += in ? __expf(v[j] - m) : 0.f;
+      d += in ? v[j] - m : 0.f;
+      above += (in && v[j] > xt) ? 1 : 0;
+    }
+  } else {
+    xt = xent_ld(xr, ti);
+    for (int c = lane; c < classes; c += 64) m = fmaxf(m, xent_ld(xr, c));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    for (int c = lane; c < classes; c += 64) {
+      const float v = xent_ld(xr, c);
+      s += __expf(v - m);
+      d += v - m;
+      above += v > xt ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o);
+    d += __shfl_xor(d, o);
+    above += __shfl_xor(above, o);
+  }
+  if (lane == 0) {
+    const float l = m + __logf(s);
+    float loss = l - xt;   // (of a dropped row: unused)
+    // lse - mean_c x_c = log(s) - sum(x_c - m) / classes
+    if (eps > 0.f) loss = (1.f - eps) * loss + eps * (__logf(s) - d / (float)classes);
+    lse[r] = l;
+    rowloss[r] = kept ? loss : 0.f;
+    meta[r] = kept ? above : (ignored ? kXentIgnored : kXentInvalid);
+  }
+}
+
+// One block. Thread i sums rows i, i + 256, ... in order; then a fixed butterfly inside each wave
+// and the four wave partials in order (one barrier).
+__global__ __launch_bounds__(256) void xent_ex_finalize_kernel(
+    const float* __restrict__ rowloss, const int* __restrict__ meta, int rows,
+    float* __restrict__ loss, float* __restrict__ inv_kept, long long* __restrict__ stats) {
+  __shared__ float sl[4];
+  __shared__ int sc[4][4];
+  const int tid = threadIdx.x;
+  float l = 0.f;
+  int cnt[4] = {0, 0, 0, 0};   // kept, top1, top5, invalid
+  for (int r = tid; r < rows; r += 256) {
+    const int k = meta[r];
+    l += rowloss[r];
+    cnt[0] += k >= 0;
+    cnt[1] += k == 0;
+    cnt[2] += k >= 0 && k < 5;
+    cnt[3] += k == kXentInvalid;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    l += __shfl_xor(l, o);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cnt[q] += __shfl_xor(cnt[q], o);
+  }
+  if ((tid & 63) == 0) {
+    sl[tid >> 6] = l;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sc[q][tid >> 6] = cnt[q];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const float sum = ((sl[0] + sl[1]) + sl[2]) + sl[3];
+    int tot[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tot[q] = sc[q][0] + sc[q][1] + sc[q][2] + sc[q][3];
+    const float n = (float)tot[0];
+    *loss = sum / n;   // 0 / 0 = NaN when every row was dropped
+    *inv_kept = tot[0] > 0 ? 1.f / n : 0.f;
+    if (stats != nullptr) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) stats[q] = stats[q] + (long long)tot[q];
+    }
+  }
+}
+
+// rows * classes < 2^31 (checked by the launcher): 32-bit index arithmetic
+template <typename T>
+__global__ __launch_bounds__(256) void xent_ex_bwd_kernel(
+    const T* __restrict__ x, const long long* __restrict__ y, const float* __restrict__ lse,
+    const int* __restrict__ meta, const float* __restrict__ inv_kept,
+    const float* __restrict__ gout, T* __restrict__ dx, unsigned n, unsigned classes, float eps,
+    float eps_c) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const unsigned r = i / classes, c = i - r * classes;
+  // every load is issued before the keep test (all in flight at once); the label is only
+  // compared, never used as an index
+  long long t = y[r];
+  int mt = meta[r];
+  float xi = xent_ld(x, (long long)i), l = lse[r];
+  float scale = (*gout) * (*inv_kept);
+  // (keeps the loads above the keep test: sunk below it they would wait for meta[r] first)
+  asm volatile("" : "+v"(xi), "+v"(l), "+v"(t), "+v"(mt), "+v"(scale));
+  const bool kept = mt >= 0;
+  const float hot = (long long)c == t ? 1.f - eps : 0.f;
+  const float v = kept ? scale * (__expf(xi - l) - hot - eps_c) : 0.f;
+  if constexpr (sizeof(T) == 2) {
+    const uint32_t u = __float_as_uint(v);
+    dx[i] = (T)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);   // round to nearest even
+  } else {
+    dx[i] = v;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// dtype: 0 = f32, 1 = bf16 logits [rows][classes]; y: int64 [rows]; rowloss, lse: fp32 [rows];
+// meta: int32 [rows]
+hipError_t arena_xent_ex_fwd(int dtype, const void* x, const long long* y, float* rowloss,
+                             float* lse, int* meta, int rows, int classes, int has_ignore,
+                             long long ignore_index, float eps, hipStream_t stream) {
+  if (rows <= 0 || classes <= 0 || !(eps >= 0.f && eps <= 1.f)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+#define XENT_LAUNCH(T, NPL)                                                                     \
+  hipLaunchKernelGGL((xent_ex_fwd_kernel<T, NPL>), grid, block, 0, stream,                      \
+                     static_cast<const T*>(x), y, rowloss, lse, meta, rows, classes,            \
+                     has_ignore, ignore_index, eps)
+  if (dtype == 1) {
+    if (classes <= 64 * 16) XENT_LAUNCH(uint16_t, 16);
+    else XENT_LAUNCH(uint16_t, 0);
+  } else {
+    if (classes <= 64 * 16) XENT_LAUNCH(float, 16);
+    else XENT_LAUNCH(float, 0);
+  }
+#undef XENT_LAUNCH
+  return hipGetLastError();
+}
+
+// loss, inv_kept: fp32 scalars; stats: int64 [4] = [kept, top1, top5, invalid] (added to) or null
+hipError_t arena_xent_ex_finalize(const float* rowloss, const int* meta, int rows, float* loss,
+                                  float* inv_kept, long long* stats, hipStream_t stream) {
+  if (rows <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(xent_ex_finalize_kernel, dim3(1), dim3(256), 0, stream, rowloss, meta, rows,
+                     loss, inv_kept, stats);
+  return hipGetLastError();
+}
+
+hipError_t arena_xent_ex_bwd(int dtype, const void* x, const long long* y, const float* lse,
+                             const int* meta, const float* inv_kept, const float* gout, void* dx,
+                             int rows, int classes, float eps, hipStream_t stream) {
+  if (rows <= 0 || classes <= 0) return hipErrorInvalidValue;
+  const long long n = (long long)rows * classes;
+  if (n >= (1ll << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  const float eps_c = eps / (float)classes;
+  if (dtype == 1)
+    hipLaunchKernelGGL(xent_ex_bwd_kernel<uint16_t>, grid, dim3(256), 0, stream,
+                       static_cast<const uint16_t*>(x), y, lse, meta, inv_kept, gout,
+                       static_cast<uint16_t*>(dx), (unsigned)n, (unsigned)classes, eps, eps_c);
+  else
+    hipLaunchKernelGGL(xent_ex_bwd_kernel<float>, grid, dim3(256), 0, stream,
+                       static_cast<const float*>(x), y, lse, meta, inv_kept, gout,
+                       static_cast<float*>(dx), (unsigned)n, (unsigned)classes, eps, eps_c);
+  return hipGetLastError();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
 // Backward of the global average pool: dx[n, p, c] = g[n, c] / HW for every pixel p of a
 // channels_last [N, HW, C] tensor, 8 channels (16 bytes of bf16) per thread -- one write pass
 // (the stock broadcast-and-copy wrote it at ~1.2 TB/s through torch's non-vectorised copy kernel).
