@@ -193,9 +193,11 @@ def conv2d_fwd(x: Tensor, w: Tensor, stride: int = 1, pad: int = 0, variant: int
         bx, bm, bmu = bn
         with_stats = True
     fin = bool(final and with_stats and bn is None and addend is None)
-    out = _ext.load().conv_fwd(x, w, int(stride), int(pad), int(variant), bool(with_stats),
-                               addend, bx, bm, bmu, addmask if addend is not None else None,
-                               stats_final=fin, bn_acc=bn_acc if bn is not None else None)
+    out = _ext.load().conv_fwd(x, w, int(stride), int(pad), int(pad), 0, 0, int(variant),
+                               bool(with_stats), addend=addend,
+                               addmask=addmask if addend is not None else None,
+                               bn_x=bx, bn_mask=bm, bn_mean=bmu,
+                               bn_acc=bn_acc if bn is not None else None, stats_final=fin)
     if bn is not None and bn_acc is not None:
         return out[0], None          # the sums went into the caller's bn_acc
     if fin:
@@ -359,8 +361,8 @@ def conv2d_bwd_data_strided(dy: Tensor, w: Tensor, x_hw: Tuple[int, int], stride
         return dx
     for wp, (ph_, pw_, Hp, Wp, a, b) in geo:
         v = variant if variant >= 0 else pick_variant(N * Hp * Wp, Cin)
-        ext.conv_fwd_ex(dy, wp, 1, ph_, pw_, Hp, Wp, int(v), False, addend, dx,
-                        [stride, stride, a, b] + ([1] if sib else []), False)
+        ext.conv_fwd(dy, wp, 1, ph_, pw_, Hp, Wp, int(v), False, addend=addend, y_out=dx,
+                     y_map=[stride, stride, a, b] + ([1] if sib else []))
     return dx
 
 
@@ -413,8 +415,8 @@ class _StemFn(torch.autograd.Function):
         Ho, Wo = z.shape[2], z.shape[3]
         fin = bool(want_stats and _use_acc(z.shape[0] * Ho * Wo, fwd_variant,
                                             w16.shape[0]))
-        out = _ext.load().conv_fwd_ex(z, w16, 1, 2, 2, Ho, Wo, int(fwd_variant), bool(want_stats),
-                                      None, None, [], True, stats_final=fin)
+        out = _ext.load().conv_fwd(z, w16, 1, 2, 2, Ho, Wo, int(fwd_variant), bool(want_stats),
+                                   stats_final=fin, c16=True)
         ctx.save_for_backward(z)
         ctx.wgrad_cfg = wgrad_cfg
         ctx.set_materialize_grads(False)
@@ -429,7 +431,8 @@ class _StemFn(torch.autograd.Function):
         (z,) = ctx.saved_tensors
         v, sp = ctx.wgrad_cfg
         dy = dy.contiguous(memory_format=torch.channels_last)
-        dw = _ext.load().conv_wgrad_ex(z, dy, 4, 4, 1, 2, 2, int(v), int(sp), False, 1.0, True)
+        dw = _ext.load().conv_wgrad(z, dy, 4, 4, 1, 2, 2, int(v), int(sp), False, 1.0, c16=True,
+                                    explicit_out=True)
         return None, dw, None, None, None
 
 
@@ -595,8 +598,8 @@ def conv2d_wgrad(x: Tensor, dy: Tensor, kernel: Tuple[int, int], stride: int = 1
     if variant < 0:
         variant = wgrad_variants_for(x.shape[1], dy.shape[1])[0]
     return _ext.load().conv_wgrad(x, dy, int(kernel[0]), int(kernel[1]), int(stride), int(pad),
-                                  int(variant), int(splits), out_dtype == torch.float32,
-                                  float(scale))
+                                  int(pad), int(variant), int(splits),
+                                  out_dtype == torch.float32, float(scale))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1176,12 +1179,12 @@ def _stem_plan(z: Tensor, w16: Tensor) -> Tuple[int, Tuple[int, int]]:
         return plan
 
     def tune() -> dict:
-        tf = {v: _time(lambda: ext.conv_fwd_ex(z, w16, 1, 2, 2, ho, wo, v, True, None, None, [],
-                                                True)) for v in fvs}
+        tf = {v: _time(lambda: ext.conv_fwd(z, w16, 1, 2, 2, ho, wo, v, True, c16=True))
+              for v in fvs}
         dy = torch.randn(z.shape[0], w16.shape[0], ho, wo, device=z.device,
                          dtype=z.dtype).contiguous(memory_format=torch.channels_last)
-        tw = {c: _time(lambda: ext.conv_wgrad_ex(z, dy, 4, 4, 1, 2, 2, c[0], c[1], False, 1.0,
-                                                 True)) for c in wcs}
+        tw = {c: _time(lambda: ext.conv_wgrad(z, dy, 4, 4, 1, 2, 2, c[0], c[1], False, 1.0,
+                                              c16=True, explicit_out=True)) for c in wcs}
         if os.environ.get("ARENA_CONV_LOG") == "1":
             print(f"stem {tuple(z.shape)}: {tf} {tw}", flush=True)
         return {"fwd": min(tf, key=tf.get), "wgrad": list(min(tw, key=tw.get))}

@@ -1,6 +1,9 @@
 // Plain-C ABI shared by the HIP kernel TUs and the host binding TU (no device code here).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#include <hip/hip_runtime_api.h>
 
 // BatchNorm statistics accumulators ("acc mode", bn_kernels.hip / conv_kernels.hip): every fp64
 // set is ARENA_ACC_REP consecutive [2][C] replicas; a consumer sums all of them, in replica order.
@@ -8,6 +11,16 @@
 // replica mt % ARENA_ACC_REP, so their same-address fp64 atomics do not serialize; the BN passes'
 // reductions (at most 512 block sums per channel) add into replica 0.
 #define ARENA_ACC_REP 4
+
+// Forward-convolution variant codes (conv_kernels.hip; arena_amd/ops/conv.py TILES mirrors them and
+// tests/test_conv.py checks the copy against arena_conv_tile):
+//   v1 tile t (0 .. ARENA_CONV_V1_TILES - 1) with its K steps split over ks blocks:
+//     t + ARENA_CONV_V1_TILES * (ks - 1), below ARENA_CONV_V1_END;
+//   v2 tile i (0 .. ARENA_CONV_V2_COUNT - 1), never split: ARENA_CONV_V2_BASE + i.
+#define ARENA_CONV_V1_TILES 16
+#define ARENA_CONV_V1_END 256
+#define ARENA_CONV_V2_BASE 4096
+#define ARENA_CONV_V2_COUNT 19
 
 // ----------------------------------------------------------------------------------------------
 // Host-visible plain-C ABI structs shared with the torch binding TU (bindings.cpp).
@@ -136,4 +149,166 @@ struct ArenaXgmiPeers {
   int push;
   long long timeout_cycles;           // barrier wait bound in s_memrealtime ticks (100 MHz)
 };
+
+// ----------------------------------------------------------------------------------------------
+// Every host-callable launcher, declared once: each .hip unit includes this header ahead of its
+// definitions (a mismatch is a "conflicting types" compile error there) and bindings.cpp calls
+// through it. Names only -- what the arguments mean is documented at the definitions.
+// ----------------------------------------------------------------------------------------------
+// csrc/ops/mlp_kernels.hip
+hipError_t arena_linear_fwd(ArenaRowSource src, const float* W, const float* bias, float* Y, int M,
+                            int N, int K, int act, float keep_prob, uint32_t seed,
+                            const long long* step_src, hipStream_t stream);
+hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float* bias, float* Y,
+                                int M, int N, int K, float keep_prob, uint32_t seed,
+                                const long long* step_src, const float* W2, float* W2_copy, int C,
+                                float* logits2, uint8_t* xb, const void* lab_ptr, int lab_dtype,
+                                int* yb, ArenaCounterOp ctr, const int* rows, hipStream_t stream);
+hipError_t arena_xent_head(const float* H, int M, int D, const float* W2, const float* b2, int C,
+                           ArenaRowSource lab, float* dlogits, float* dZ, float keep_prob,
+                           int relu_mask, float loss_scale, float* loss_acc, int* correct_acc,
+                           int hist_len, const long long* hist_step, ArenaCounterOp ctr,
+                           hipStream_t stream);
+hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam adam,
+                               float grad_scale, ArenaCounterOp ctr, ArenaHead head,
+                               hipStream_t stream);
+hipError_t arena_adam_flat(float* P, float* M, float* V, const float* G, long long n,
+                           ArenaAdam adam, ArenaCounterOp ctr, hipStream_t stream);
+hipError_t arena_sgd_flat(float* P, const float* G, long long n, float lr, const float* lr_ptr,
+                          float gscale, hipStream_t stream);
+hipError_t arena_softmax_xent(const float* logits, const long long* labels, int M, int C,
+                              float* loss, float* dlogits, float grad_scale, hipStream_t stream);
+hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const long long* ns,
+                               int count, float* flat, float scale, int dir, hipStream_t stream);
+hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, const long long* ns,
+                               int count, float* master, float* mom, void* wbf, float lr, float mu,
+                               float wd, hipStream_t stream);
+hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
+                           long long n, float lr, float mu, float wd, float scale,
+                           hipStream_t stream);
+#ifdef ARENA_TIMELINE
+hipError_t arena_timeline_read(long long* host, int clear);
+#endif
+
+// csrc/ops/bn_kernels.hip
+void arena_bn_set_fin_max_blocks(int p);
+void arena_bn_set_nt(int on);
+void arena_bn_set_elem_max_blocks(int b);
+void arena_bn_set_dx_max_blocks(int b);
+void arena_bn_set_slice(int on);
+void arena_bn_set_pool_quad_mult(int m);
+void arena_bn_set_acc_max_pairs(long long p);
+long long arena_bn_acc_max_pairs();
+int arena_bn_acc_ok(long long M, int C);
+void arena_bn_set_reduce_geometry(long long max_blocks, long long min_rounds);
+long long arena_bn_lvl2_doubles(long long nblk, int C);
+long long arena_bn_workspace_floats(long long M, int C);
+hipError_t arena_bn_fwd(int dtype, const void* x, const void* res, void* y, uint8_t* mask,
+                        long long M, int C, int relu, int training, float* part, int ext_nblk,
+                        long long ext_rpb, double* lvl2, unsigned* tickets, ArenaBNStats st,
+                        double* acc, int acc_ready, double* zero, int nzero, hipStream_t stream);
+hipError_t arena_bn_bwd(int dtype, const void* dy, const uint8_t* mask, const void* x, void* dx,
+                        void* dres, long long M, int C, int relu, float* part, int ext_nblk,
+                        double* lvl2, unsigned* tickets, ArenaBNBwd co, double* acc, int fin_dx,
+                        double* zero, int nzero, const void* x2, const float* mean2,
+                        double* acc2, hipStream_t stream);
+hipError_t arena_bn_pool_fwd(int dtype, const void* x, void* y, uint8_t* pos, void* xsel, int N,
+                             int H, int W, int C, int k, int s, int p, ArenaBNStats st,
+                             const double* fin, const float* part, int ext_nblk, long long ext_rpb,
+                             double* lvl2, unsigned* tickets, double* zero, int nzero,
+                             hipStream_t stream);
+hipError_t arena_bn_pool_bwd(int dtype, const void* dy, const uint8_t* pos, const void* x,
+                             const void* xsel, void* dx, int N, int H, int W, int C, int k, int s,
+                             int p, ArenaBNBwd co, double* acc, double* zero, int nzero,
+                             hipStream_t stream);
+
+// csrc/ops/pool_kernels.hip
+hipError_t arena_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* pos, int N, int H, int W,
+                             int C, int k, int s, int p, hipStream_t stream);
+hipError_t arena_maxpool_bwd(int dtype, const void* dy, const uint8_t* pos, void* dx, int N, int H,
+                             int W, int C, int k, int s, int p, hipStream_t stream);
+hipError_t arena_xent_fwd(int dtype, const void* x, const long long* y, float* rowloss,
+                          float* lse, int rows, int classes, hipStream_t stream);
+hipError_t arena_xent_bwd(int dtype, const void* x, const long long* y, const float* lse,
+                          const float* gout, void* dx, int rows, int classes, hipStream_t stream);
+hipError_t arena_xent_ex_fwd(int dtype, const void* x, const long long* y, float* rowloss,
+                             float* lse, int* meta, int rows, int classes, int has_ignore,
+                             long long ignore_index, float eps, hipStream_t stream);
+hipError_t arena_xent_ex_finalize(const float* rowloss, const int* meta, int rows, float* loss,
+                                  float* inv_kept, long long* stats, hipStream_t stream);
+hipError_t arena_xent_ex_bwd(int dtype, const void* x, const long long* y, const float* lse,
+                             const int* meta, const float* inv_kept, const float* gout, void* dx,
+                             int rows, int classes, float eps, hipStream_t stream);
+hipError_t arena_gap_bwd(int dtype, const void* g, void* dx, int N, int HW, int C, float scale,
+                         hipStream_t stream);
+
+// csrc/ops/conv_kernels.hip
+void arena_conv_set_stats_one_pass(int on);
+void arena_conv_set_dbg(int bits);
+hipError_t arena_conv_fwd_ex(const void* x, const void* w, void* y, float* part, const void* add,
+                             const uint8_t* addmask, const void* bnx, const uint8_t* bnmask,
+                             const float* bnmean, int N, int H, int W, int C, int Cout, int R,
+                             int S, int stride, int pad_h, int pad_w, int Ho, int Wo,
+                             const int* y_map, int c16, int variant, double* bn_acc, int ksplit,
+                             void* kws, unsigned* kcnt, hipStream_t st);
+hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N, int H, int W,
+                                 int C, int Cout, int Hy, int Wy, int osh, int osw, int nph,
+                                 const void* const* w, const int* R, const int* S,
+                                 const int* pad_h, const int* pad_w, const int* Ho, const int* Wo,
+                                 const int* ooh, const int* oow, int variant, hipStream_t st);
+int arena_conv_tile(int variant, int* bm, int* bn);
+long long arena_conv_fwd_ksplit_floats(long long M, int Cout, int variant, int ksplit);
+long long arena_conv_fwd_tiles(long long M, int Cout, int variant);
+int arena_conv_fwd_tile_rows(int variant);
+hipError_t arena_conv_flip_multi(int n, const void* const* src, void* const* dst, const int* cout,
+                                 const int* cin, const int* rs, hipStream_t st);
+hipError_t arena_conv_phase_weights(const void* w, void* wt, int Cout, int C, int R, int S,
+                                    int stride, int pad, long long* total, hipStream_t st);
+hipError_t arena_conv_flip_weight(const void* w, void* wt, int Cout, int C, int R, int S,
+                                  hipStream_t st);
+hipError_t arena_s2d_stem(const void* x, void* z, int N, int H, int W, int C, int in_f32,
+                          hipStream_t st);
+hipError_t arena_stem_weight(const void* w, void* w16, int Cout, int C, long long sco,
+                             long long sc, long long sr, long long ss, int w_f32, hipStream_t st);
+hipError_t arena_stem_weight_grad(const void* dw16, void* dw, int Cout, int C, long long dco,
+                                  long long dc, long long dr, long long ds, int dw_f32,
+                                  hipStream_t st);
+int arena_conv_wgrad_tile(int variant, int* bm, int* bn);
+int arena_conv_wgrad_splits(int N, int Ho, int Wo, int Cout, int Ktot, int variant,
+                            int splits_hint);
+hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* dw_bf16,
+                               float* dw_f32, int N, int H, int W, int C, int Cout, int R, int S,
+                               int stride, int pad_h, int pad_w, int Ho, int Wo, int c16,
+                               int variant, int splits_hint, float scale, hipStream_t st);
+
+// csrc/ccl/xgmi_ccl.hip
+hipError_t arena_ccl_malloc(void** p, size_t bytes, int uncached);
+hipError_t arena_ccl_free(void* p);
+hipError_t arena_ccl_memset(void* p, int v, size_t bytes);
+hipError_t arena_ccl_ipc_get(void* p, void* handle);
+hipError_t arena_ccl_ipc_open(const void* handle, void** p);
+hipError_t arena_ccl_ipc_close(void* p);
+hipError_t arena_ccl_allreduce(const ArenaXgmiPeers* P, const float* in, float* out, long long n,
+                               float scale, hipStream_t stream);
+void arena_ccl_set_oneshot_max(long long e);
+long long arena_ccl_get_oneshot_max();
+hipError_t arena_ccl_adam(const ArenaXgmiPeers* P, float* M, float* V, long long n, ArenaAdam a,
+                          ArenaCounterOp ctr, hipStream_t stream);
+void arena_ccl_set_block_elems(long long e);
+void arena_ccl_set_max_blocks(int b);
+hipError_t arena_ccl_broadcast(const ArenaXgmiPeers* P, const float* in, float* out, long long n,
+                               int root, hipStream_t stream);
+void arena_ccl_set_bcast_direct_max(long long e);
+hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom, long long off,
+                              long long n, float lr, float momentum, float wd, float scale,
+                              hipStream_t stream);
+void arena_ccl_sgd_shard(long long off, long long n, int world, int r, long long* lo,
+                         long long* hi);
+hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off, long long n,
+                             float lr, float momentum, float wd, float scale, hipStream_t stream);
+void arena_ccl_sgd_f32_shard(long long off, long long n, int world, int r, long long* lo,
+                             long long* hi);
+hipError_t arena_ccl_allgather(const ArenaXgmiPeers* P, const float* in, float* out, long long m,
+                               hipStream_t stream);
+void arena_ccl_shard(long long n, int world, int r, long long* lo, long long* hi);
 }  // extern "C"

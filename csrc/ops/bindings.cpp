@@ -1,6 +1,7 @@
 // PyTorch binding for the arena_amd HIP kernels. Validates every shape/dtype/device on the host
 // BEFORE launching (a kernel that faults on an MI355X can reset the node), then calls the plain-C
-// launchers in mlp_kernels.hip on the current HIP stream (so hipGraph capture via torch works).
+// launchers of the .hip units (declared once, in abi.h) on the current HIP stream (so hipGraph
+// capture via torch works).
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime_api.h>
@@ -10,133 +11,6 @@
 #include <vector>
 
 #include "abi.h"
-
-extern "C" {
-hipError_t arena_linear_fwd(ArenaRowSource, const float*, const float*, float*, int, int, int, int,
-                            float, uint32_t, const long long*, hipStream_t);
-hipError_t arena_mlp_fwd_logits(ArenaRowSource, const float*, const float*, float*, int, int, int,
-                                float, uint32_t, const long long*, const float*, float*, int,
-                                float*, uint8_t*, const void*, int, int*, ArenaCounterOp,
-                                const int*, hipStream_t);
-hipError_t arena_xent_head(const float*, int, int, const float*, const float*, int, ArenaRowSource,
-                           float*, float*, float, int, float, float*, int*, int, const long long*,
-                           ArenaCounterOp, hipStream_t);
-hipError_t arena_wgrad_grouped(ArenaWGradProblem*, int, ArenaAdam, float, ArenaCounterOp, ArenaHead,
-                               hipStream_t);
-hipError_t arena_adam_flat(float*, float*, float*, const float*, long long, ArenaAdam,
-                           ArenaCounterOp, hipStream_t);
-hipError_t arena_sgd_flat(float*, const float*, long long, float, const float*, float, hipStream_t);
-hipError_t arena_softmax_xent(const float*, const long long*, int, int, float*, float*, float,
-                              hipStream_t);
-hipError_t arena_mt_copy_scale(float* const*, const long long*, const long long*, int, float*, float,
-                               int, hipStream_t);
-hipError_t arena_mt_sgd_master(const void* const*, const long long*, const long long*, int,
-                               float*, float*, void*, float, float, float, hipStream_t);
-hipError_t arena_shard_sgd(const void*, int, float*, float*, void*, long long, float, float, float,
-                           float, hipStream_t);
-// csrc/ccl/xgmi_ccl.hip
-hipError_t arena_ccl_malloc(void**, size_t, int);
-hipError_t arena_ccl_free(void*);
-hipError_t arena_ccl_memset(void*, int, size_t);
-hipError_t arena_ccl_ipc_get(void*, void*);
-hipError_t arena_ccl_ipc_open(const void*, void**);
-hipError_t arena_ccl_ipc_close(void*);
-hipError_t arena_ccl_allreduce(const ArenaXgmiPeers*, const float*, float*, long long, float,
-                               hipStream_t);
-hipError_t arena_ccl_adam(const ArenaXgmiPeers*, float*, float*, long long, ArenaAdam,
-                          ArenaCounterOp, hipStream_t);
-void arena_ccl_shard(long long, int, int, long long*, long long*);
-hipError_t arena_ccl_broadcast(const ArenaXgmiPeers*, const float*, float*, long long, int,
-                               hipStream_t);
-hipError_t arena_ccl_allgather(const ArenaXgmiPeers*, const float*, float*, long long,
-                               hipStream_t);
-void arena_ccl_set_bcast_direct_max(long long);
-hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers*, float*, float*, long long, long long, float,
-                              float, float, float, hipStream_t);
-void arena_ccl_sgd_shard(long long, long long, int, int, long long*, long long*);
-hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers*, float*, long long, long long, float, float,
-                             float, float, hipStream_t);
-void arena_ccl_sgd_f32_shard(long long, long long, int, int, long long*, long long*);
-void arena_ccl_set_block_elems(long long);
-void arena_ccl_set_max_blocks(int);
-void arena_bn_set_elem_max_blocks(int);
-void arena_bn_set_dx_max_blocks(int);
-void arena_bn_set_slice(int);
-void arena_ccl_set_oneshot_max(long long);
-long long arena_ccl_get_oneshot_max();
-// csrc/ops/conv_kernels.hip
-hipError_t arena_conv_fwd(const void*, const void*, void*, float*, const void*, const void*,
-                          const uint8_t*, const float*, int, int, int, int, int, int, int, int,
-                          int, int, hipStream_t);
-hipError_t arena_conv_flip_weight(const void*, void*, int, int, int, int, hipStream_t);
-hipError_t arena_conv_flip_multi(int, const void* const*, void* const*, const int*, const int*,
-                                 const int*, hipStream_t);
-hipError_t arena_conv_fwd_ex(const void*, const void*, void*, float*, const void*, const uint8_t*,
-                             const void*, const uint8_t*, const float*, int, int, int, int, int,
-                             int, int, int, int, int, int, int, const int*, int, int, double*,
-                             int, void*, unsigned*, hipStream_t);
-hipError_t arena_conv_fwd_phases(const void*, void*, const void*, int, int, int, int, int, int,
-                                 int, int, int, int, const void* const*, const int*, const int*,
-                                 const int*, const int*, const int*, const int*, const int*,
-                                 const int*, int, hipStream_t);
-long long arena_conv_fwd_ksplit_floats(long long, int, int, int);
-void arena_conv_set_stats_one_pass(int);
-void arena_conv_set_dbg(int);
-long long arena_conv_fwd_tiles(long long, int, int);
-int arena_conv_fwd_tile_rows(int);
-hipError_t arena_conv_wgrad_ex(const void*, const void*, float*, void*, float*, int, int, int, int,
-                               int, int, int, int, int, int, int, int, int, int, int, float,
-                               hipStream_t);
-hipError_t arena_s2d_stem(const void*, void*, int, int, int, int, int, hipStream_t);
-hipError_t arena_stem_weight(const void*, void*, int, int, long long, long long, long long,
-                             long long, int, hipStream_t);
-hipError_t arena_stem_weight_grad(const void*, void*, int, int, long long, long long, long long,
-                                  long long, int, hipStream_t);
-hipError_t arena_conv_phase_weights(const void*, void*, int, int, int, int, int, int, long long*,
-                                    hipStream_t);
-int arena_conv_wgrad_splits(int, int, int, int, int, int, int);
-hipError_t arena_conv_wgrad(const void*, const void*, float*, void*, float*, int, int, int, int,
-                            int, int, int, int, int, int, int, float, hipStream_t);
-// csrc/ops/bn_kernels.hip
-long long arena_bn_workspace_floats(long long, int);
-long long arena_bn_lvl2_doubles(long long, int);
-void arena_bn_set_reduce_geometry(long long, long long);
-void arena_bn_set_fin_max_blocks(int);
-void arena_bn_set_nt(int);
-void arena_bn_set_pool_quad_mult(int);
-// csrc/ops/pool_kernels.hip
-hipError_t arena_maxpool_fwd(int, const void*, void*, uint8_t*, int, int, int, int, int, int, int,
-                             hipStream_t);
-hipError_t arena_maxpool_bwd(int, const void*, const uint8_t*, void*, int, int, int, int, int, int,
-                             int, hipStream_t);
-hipError_t arena_xent_fwd(int, const void*, const long long*, float*, float*, int, int,
-                          hipStream_t);
-hipError_t arena_gap_bwd(int, const void*, void*, int, int, int, float, hipStream_t);
-hipError_t arena_xent_bwd(int, const void*, const long long*, const float*, const float*, void*,
-                          int, int, hipStream_t);
-hipError_t arena_xent_ex_fwd(int, const void*, const long long*, float*, float*, int*, int, int,
-                             int, long long, float, hipStream_t);
-hipError_t arena_xent_ex_finalize(const float*, const int*, int, float*, float*, long long*,
-                                  hipStream_t);
-hipError_t arena_xent_ex_bwd(int, const void*, const long long*, const float*, const int*,
-                             const float*, const float*, void*, int, int, float, hipStream_t);
-hipError_t arena_bn_fwd(int, const void*, const void*, void*, uint8_t*, long long, int, int, int,
-                        float*, int, long long, double*, unsigned*, ArenaBNStats, double*, int,
-                        double*, int, hipStream_t);
-hipError_t arena_bn_bwd(int, const void*, const uint8_t*, const void*, void*, void*, long long, int,
-                        int, float*, int, double*, unsigned*, ArenaBNBwd, double*, int, double*,
-                        int, const void*, const float*, double*, hipStream_t);
-int arena_bn_acc_ok(long long, int);
-hipError_t arena_bn_pool_fwd(int, const void*, void*, uint8_t*, void*, int, int, int, int, int, int,
-                             int, ArenaBNStats, const double*, const float*, int, long long,
-                             double*, unsigned*, double*, int, hipStream_t);
-hipError_t arena_bn_pool_bwd(int, const void*, const uint8_t*, const void*, const void*, void*, int,
-                             int, int, int, int, int, int, ArenaBNBwd, double*, double*, int,
-                             hipStream_t);
-#ifdef ARENA_TIMELINE
-hipError_t arena_timeline_read(long long*, int);
-#endif
-}
 
 namespace {
 
@@ -883,8 +757,8 @@ unsigned* conv_tickets(const Tensor& like, int64_t tiles) {
   return p;
 }
 
-// conv variant code: v1 tile/pipeline variant (0..15) + 16 * (ksplit - 1); 4096 + i: the v2 tile
-// kernel's variant i (never split)
+// conv variant code (abi.h ARENA_CONV_*): a v1 tile/pipeline variant + its split-K factor, or a
+// variant of the v2 tile kernel (conv_kernels.hip conv2_body; never split)
 struct ConvSplit {
   int base = 0, ks = 1;
   Tensor ws;
@@ -894,15 +768,18 @@ struct ConvSplit {
 ConvSplit conv_split(const Tensor& x, int64_t variant, int64_t M, int64_t Cout, int64_t Ktot) {
   ConvSplit s;
   TORCH_CHECK(variant >= 0, "conv: bad variant ", variant);
-  if (variant >= 4096) {   // v2 tile kernel (conv_kernels.hip conv2_body): 4096 + i
-    TORCH_CHECK(variant - 4096 < 19, "conv: unknown v2 variant ", variant);
+  if (variant >= ARENA_CONV_V2_BASE) {
+    TORCH_CHECK(variant - ARENA_CONV_V2_BASE < ARENA_CONV_V2_COUNT, "conv: unknown v2 variant ",
+                variant);
     s.base = (int)variant;
-  } else {   // v1 tile i (0..15), its K steps split over ks blocks: i + 16 (ks - 1)
-    TORCH_CHECK(variant < 256, "conv: unknown variant ", variant);
-    s.base = (int)(variant % 16);
-    s.ks = (int)(variant / 16) + 1;
-    TORCH_CHECK((s.base & 1) || Cout % 128 == 0, "conv: variant ", variant,
-                " needs Cout % 128 == 0 (Cout = ", Cout, ")");
+  } else {
+    TORCH_CHECK(variant < ARENA_CONV_V1_END, "conv: unknown variant ", variant);
+    s.base = (int)(variant % ARENA_CONV_V1_TILES);
+    s.ks = (int)(variant / ARENA_CONV_V1_TILES) + 1;
+    int bm = 0, bn = 0;
+    arena_conv_tile(s.base, &bm, &bn);
+    TORCH_CHECK(Cout % bn == 0, "conv: variant ", variant, " needs Cout % ", bn,
+                " == 0 (Cout = ", Cout, ")");
   }
   if (s.ks > 1) {
     TORCH_CHECK(s.ks <= Ktot / 64, "conv: split-K ", s.ks, " exceeds the ", Ktot / 64,
@@ -1305,9 +1182,26 @@ void pool_check(const Tensor& t, const char* name) {
   TORCH_CHECK(t.size(1) % 8 == 0, name, ": C must be a multiple of 8");
 }
 
-// Returns (y, pos): pos = uint8 in-window argmax, same NHWC layout as y.
-// NHWC bf16 implicit-GEMM convolution (csrc/ops/conv_kernels.hip). x: [N,C,H,W] channels_last,
-// w: [Cout,C,R,S] channels_last (memory order [Cout][R][S][C]).
+// ------------------------------------------------------------------- NHWC bf16 convolutions
+// Every activation / weight / gradient operand of the conv kernels.
+void check_nhwc_bf16(const Tensor& t, const char* name, const torch::Device& dev) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev && t.dim() == 4 &&
+                  t.scalar_type() == torch::kBFloat16 &&
+                  t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              name, " must be a channels_last bf16 4-D tensor on ", dev);
+}
+
+// A bit-packed mask over the elements of y (bit i of byte v: element 8 v + i, NHWC order).
+void check_bitmask(const Tensor& m, const char* name, const Tensor& y) {
+  TORCH_CHECK(m.scalar_type() == torch::kUInt8 && m.is_contiguous() && m.device() == y.device() &&
+                  m.numel() == y.numel() / 8,
+              name, " must be uint8 with numel(y) / 8 bytes on y's device");
+}
+
+// NHWC bf16 implicit-GEMM convolution (csrc/ops/conv_kernels.hip arena_conv_fwd_ex). x: [N,C,H,W]
+// channels_last, w: [Cout,C,R,S] channels_last (memory order [Cout][R][S][C]).
+// pad_h/pad_w: top/left padding; Ho/Wo: the output size, or 0, 0 for that of a convolution padded
+// by pad_h/pad_w on both sides.
 // with_stats: also returns the BatchNorm partials of y ([ceil(M/BM)][2][Cout] fp32, BM rows per
 // partial) for bn_fwd(..., stats_part, BM): the BN layer after the conv skips its stats pass.
 // addend (optional): bf16 tensor shaped like y (channels_last) added to the fp32 sums before the
@@ -1318,83 +1212,107 @@ void pool_check(const Tensor& t, const char* name) {
 // stats_final (with with_stats, forward statistics only): the second output is the fp64 [2][Cout]
 // accumulator set (sum y, sum y^2) the epilogue added into, for bn_fwd(stats_fin=...), instead of
 // the per-tile partials.
-std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, int64_t variant,
-                             bool with_stats, OptT addend, OptT bn_x, OptT bn_mask,
-                             OptT bn_mean, OptT addmask, bool stats_final, OptT bn_acc) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4,
-              "conv_fwd: x and w must be 4-D GPU tensors");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16,
-              "conv_fwd: bfloat16 only");
-  TORCH_CHECK(x.device() == w.device(), "conv_fwd: x and w on different devices");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_fwd: x and w must be channels_last contiguous");
+// addmask (with addend): only the addend elements whose bit is set are added. bn_acc (with bn_x):
+// the BN layer's fp64 [kRep, 2, Cout] backward sums, added into instead of writing partials.
+// y_out + y_map = [osh, osw, ooh, oow]: output pixel (ho, wo) goes to (ho*osh+ooh, wo*osw+oow) of
+// the larger preallocated y_out; an optional 5th entry fill_sib = 1 also writes the untapped
+// sibling pixels of phase (0, 0) with the addend or zero. The addend is then shaped like y_out and
+// may alias it (in-place accumulate: each element is read and written by the same lane).
+// c16: the stem's form, C == 16 and S % 4 == 0.
+std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad_h, int64_t pad_w,
+                             int64_t Ho, int64_t Wo, int64_t variant, bool with_stats,
+                             OptT addend, OptT addmask, OptT bn_x, OptT bn_mask, OptT bn_mean,
+                             OptT bn_acc, bool stats_final, OptT y_out,
+                             std::vector<int64_t> y_map, bool c16) {
+  const torch::Device dev = x.device();
+  check_nhwc_bf16(x, "conv_fwd: x", dev);
+  check_nhwc_bf16(w, "conv_fwd: w", dev);
+  const bool mapped = y_out.has_value(), bwd_bn = bn_x.has_value();
+  const bool fin = with_stats && stats_final;
+  const bool bacc = bn_acc.has_value() && bn_acc->defined();
+  // combinations no kernel has: rejected here, not left to the launcher
+  TORCH_CHECK(!(mapped && (with_stats || stats_final)), "conv_fwd: statistics need a dense output");
+  TORCH_CHECK(!(bwd_bn && (mapped || c16)), "conv_fwd: the bn_x form has no y_out or c16 kernel");
+  TORCH_CHECK(addend.has_value() || !addmask.has_value(), "conv_fwd: addmask needs an addend");
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int64_t Cout = w.size(0), R = w.size(2), S = w.size(3);
   TORCH_CHECK(w.size(1) == C, "conv_fwd: weight has ", w.size(1), " input channels, x has ", C);
-  TORCH_CHECK(C % 64 == 0 && Cout % 64 == 0, "conv_fwd: C and Cout must be multiples of 64");
-  TORCH_CHECK(stride >= 1 && pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S,
-              "conv_fwd: bad stride/padding");
-  const int64_t Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+  TORCH_CHECK(Cout % 64 == 0 && (c16 ? (C == 16 && S % 4 == 0) : C % 64 == 0),
+              "conv_fwd: C and Cout must be multiples of 64 (c16 mode: C == 16, S % 4 == 0)");
+  if (Ho == 0 && Wo == 0) {
+    TORCH_CHECK(stride >= 1 && pad_h >= 0 && pad_w >= 0 && H + 2 * pad_h >= R &&
+                    W + 2 * pad_w >= S,
+                "conv_fwd: bad stride/padding");
+    Ho = (H + 2 * pad_h - R) / stride + 1;
+    Wo = (W + 2 * pad_w - S) / stride + 1;
+  }
+  TORCH_CHECK(stride >= 1 && Ho >= 1 && Wo >= 1, "conv_fwd: bad geometry");
   TORCH_CHECK(N * Ho * Wo < (int64_t(1) << 31), "conv_fwd: too many output pixels");
-  const ConvSplit ks = conv_split(x, variant, N * Ho * Wo, Cout, R * S * C);
-  Tensor y = torch::empty({N, Cout, Ho, Wo},
-                          x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  const int rows = arena_conv_fwd_tile_rows(ks.base);
-  const int64_t m_tiles = (N * Ho * Wo + rows - 1) / rows;
-  const bool fin = with_stats && stats_final;
-  TORCH_CHECK(!fin || (!bn_x.has_value() && !addend.has_value() && Cout <= kAccC),
+  TORCH_CHECK(!fin || (!bwd_bn && !addend.has_value() && Cout <= kAccC),
               "conv_fwd: stats_final is forward statistics without an addend");
-  // bn_acc (backward-data form): the BN layer's fp64 [2][Cout] backward sums, added into
-  const bool bacc = bn_acc.has_value() && bn_acc->defined();
-  if (bacc) {
-    TORCH_CHECK(bn_x.has_value() && with_stats && !fin, "conv_fwd: bn_acc is the bn_x form's");
-    TORCH_CHECK(bn_acc->is_cuda() && bn_acc->device() == x.device() &&
+  TORCH_CHECK(!bacc || (bwd_bn && with_stats && !fin), "conv_fwd: bn_acc is the bn_x form's");
+  const ConvSplit ks = conv_split(x, variant, N * Ho * Wo, Cout, R * S * C);
+  Tensor y;
+  std::vector<int> map7;
+  if (mapped) {
+    y = *y_out;
+    check_nhwc_bf16(y, "conv_fwd: y_out", dev);
+    TORCH_CHECK(y.size(0) == N && y.size(1) == Cout, "conv_fwd: y_out must be [N, Cout, Hy, Wy]");
+    TORCH_CHECK((y_map.size() == 4 || y_map.size() == 5) && y_map[0] >= 1 && y_map[1] >= 1 &&
+                    y_map[2] >= 0 && y_map[3] >= 0 && (Ho - 1) * y_map[0] + y_map[2] < y.size(2) &&
+                    (Wo - 1) * y_map[1] + y_map[3] < y.size(3),
+                "conv_fwd: y_map must place every output pixel inside y_out");
+    const bool fill = y_map.size() == 5 && y_map[4] != 0;
+    // sibling fill: phase (0, 0) whose pixels' siblings tile all of y_out
+    TORCH_CHECK(!fill || (y_map[2] == 0 && y_map[3] == 0 &&
+                          Ho == (y.size(2) + y_map[0] - 1) / y_map[0] &&
+                          Wo == (y.size(3) + y_map[1] - 1) / y_map[1]),
+                "conv_fwd: fill_sib needs phase (0, 0) covering y_out");
+    map7 = {(int)y.size(2), (int)y.size(3), (int)y_map[0], (int)y_map[1], (int)y_map[2],
+            (int)y_map[3], fill ? 1 : 0};
+  } else {
+    y = torch::empty({N, Cout, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  }
+  if (addend.has_value()) {
+    check_nhwc_bf16(*addend, "conv_fwd: addend", dev);
+    TORCH_CHECK(addend->sizes() == y.sizes(), "conv_fwd: addend must be shaped like the output");
+    if (addmask.has_value()) check_bitmask(*addmask, "conv_fwd: addmask", y);
+  }
+  if (bwd_bn) {
+    TORCH_CHECK(with_stats && bn_mean.has_value(), "conv_fwd: bn_x needs with_stats and bn_mean");
+    check_nhwc_bf16(*bn_x, "conv_fwd: bn_x", dev);
+    TORCH_CHECK(bn_x->sizes() == y.sizes(), "conv_fwd: bn_x must be shaped like the output");
+    check_f32(*bn_mean, "bn_mean");
+    TORCH_CHECK(bn_mean->numel() == Cout, "conv_fwd: bn_mean must have Cout elements");
+    if (bn_mask.has_value()) check_bitmask(*bn_mask, "conv_fwd: bn_mask", y);
+  }
+  if (bacc)
+    TORCH_CHECK(bn_acc->is_cuda() && bn_acc->device() == dev &&
                     bn_acc->scalar_type() == torch::kFloat64 && bn_acc->is_contiguous() &&
                     bn_acc->numel() == kRep * 2 * Cout,
                 "conv_fwd: bn_acc must be a contiguous fp64 [kRep, 2, Cout] set");
-  }
-  Tensor part = with_stats && !fin && !bacc
-                    ? torch::empty({m_tiles * 2 * Cout}, x.options().dtype(torch::kFloat32))
-                    : Tensor();
-  Tensor acc_t = fin ? bn_acc_set(x, Cout) : (bacc ? *bn_acc : Tensor());
-  if (addend.has_value()) {
-    TORCH_CHECK(addend->sizes() == y.sizes() && addend->scalar_type() == torch::kBFloat16 &&
-                    addend->device() == y.device() &&
-                    addend->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_fwd: addend must be a channels_last bf16 tensor shaped like the output");
-  }
-  if (bn_x.has_value()) {
-    TORCH_CHECK(with_stats && bn_mean.has_value(), "conv_fwd: bn_x needs with_stats and bn_mean");
-    TORCH_CHECK(bn_x->sizes() == y.sizes() && bn_x->scalar_type() == torch::kBFloat16 &&
-                    bn_x->device() == y.device() &&
-                    bn_x->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_fwd: bn_x must be a channels_last bf16 tensor shaped like the output");
-    check_f32(*bn_mean, "bn_mean");
-    TORCH_CHECK(bn_mean->numel() == Cout, "conv_fwd: bn_mean must have Cout elements");
-    if (bn_mask.has_value()) {
-      TORCH_CHECK(bn_mask->scalar_type() == torch::kUInt8 && bn_mask->is_contiguous() &&
-                      bn_mask->device() == y.device() && bn_mask->numel() == y.numel() / 8,
-                  "conv_fwd: bn_mask must be uint8 with numel(y) / 8 bytes");
-    }
-  }
-  if (addmask.has_value()) {
-    TORCH_CHECK(addend.has_value() && addmask->scalar_type() == torch::kUInt8 &&
-                    addmask->is_contiguous() && addmask->device() == y.device() &&
-                    addmask->numel() == y.numel() / 8,
-                "conv_fwd: addmask needs an addend and numel(y) / 8 uint8 bytes");
+  // statistics: per-tile partials, or sums into a pool set (fin) / the BN layer's own set (bacc)
+  Tensor part, acc_t;
+  if (fin) {
+    acc_t = bn_acc_set(x, Cout);
+  } else if (bacc) {
+    acc_t = *bn_acc;
+  } else if (with_stats) {
+    const int rows = arena_conv_fwd_tile_rows(ks.base);
+    const int64_t m_tiles = (N * Ho * Wo + rows - 1) / rows;
+    part = torch::empty({m_tiles * 2 * Cout}, x.options().dtype(torch::kFloat32));
   }
   check_hip(arena_conv_fwd_ex(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                               part.defined() ? part.data_ptr<float>() : nullptr,
                               addend.has_value() ? addend->data_ptr() : nullptr,
                               addmask.has_value() ? addmask->data_ptr<uint8_t>() : nullptr,
-                              bn_x.has_value() ? bn_x->data_ptr() : nullptr,
-                              bn_x.has_value() && bn_mask.has_value()
-                                  ? bn_mask->data_ptr<uint8_t>()
-                                  : nullptr,
-                              bn_x.has_value() ? bn_mean->data_ptr<float>() : nullptr,
-                              (int)N, (int)H, (int)W, (int)C, (int)Cout, (int)R, (int)S,
-                              (int)stride, (int)pad, (int)pad, 0, 0, nullptr, 0, ks.base,
+                              bwd_bn ? bn_x->data_ptr() : nullptr,
+                              bwd_bn && bn_mask.has_value() ? bn_mask->data_ptr<uint8_t>()
+                                                            : nullptr,
+                              bwd_bn ? bn_mean->data_ptr<float>() : nullptr, (int)N, (int)H,
+                              (int)W, (int)C, (int)Cout, (int)R, (int)S, (int)stride, (int)pad_h,
+                              (int)pad_w, (int)Ho, (int)Wo, mapped ? map7.data() : nullptr,
+                              c16 ? 1 : 0, ks.base,
                               acc_t.defined() ? acc_t.data_ptr<double>() : nullptr, ks.ks,
                               ks.ks > 1 ? ks.ws.data_ptr() : nullptr, ks.cnt, cur_stream()),
             "conv_fwd");
@@ -1406,9 +1324,7 @@ std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, in
 // W'[ci][co][r][s] = W[co][ci][R-1-r][S-1-s] as a channels_last [C, Cout, R, S] bf16 tensor: the
 // weight of the backward-data pass run through conv_fwd.
 Tensor conv_flip_weight(Tensor w) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.scalar_type() == torch::kBFloat16 &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_flip_weight: w must be a channels_last bf16 GPU tensor [Cout, C, R, S]");
+  check_nhwc_bf16(w, "conv_flip_weight: w", w.device());
   const int64_t Cout = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
   TORCH_CHECK(Cout % 64 == 0 && C % 64 == 0, "conv_flip_weight: C and Cout must be multiples of 64");
   Tensor wt = torch::empty({C, Cout, R, S}, w.options().memory_format(at::MemoryFormat::ChannelsLast));
@@ -1428,14 +1344,11 @@ void conv_flip_multi(std::vector<Tensor> src, std::vector<Tensor> dst) {
   for (size_t i = 0; i < src.size(); ++i) {
     const Tensor& w = src[i];
     const Tensor& d = dst[i];
-    TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.scalar_type() == torch::kBFloat16 &&
-                    w.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_flip_multi: src must be channels_last bf16 GPU tensors [Cout, C, R, S]");
-    TORCH_CHECK(d.is_cuda() && d.scalar_type() == torch::kBFloat16 && d.dim() == 4 &&
-                    d.size(0) == w.size(1) && d.size(1) == w.size(0) && d.size(2) == w.size(2) &&
-                    d.size(3) == w.size(3) && d.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                    d.get_device() == w.get_device(),
-                "conv_flip_multi: dst must be a channels_last bf16 [C, Cout, R, S] tensor");
+    check_nhwc_bf16(w, "conv_flip_multi: src", w.device());
+    check_nhwc_bf16(d, "conv_flip_multi: dst", w.device());
+    TORCH_CHECK(d.size(0) == w.size(1) && d.size(1) == w.size(0) && d.size(2) == w.size(2) &&
+                    d.size(3) == w.size(3),
+                "conv_flip_multi: dst must be [C, Cout, R, S] of its src");
     TORCH_CHECK(w.size(0) % 64 == 0 && w.size(1) % 64 == 0 && w.size(2) * w.size(3) <= 64,
                 "conv_flip_multi: C and Cout must be multiples of 64, R*S <= 64");
     sp.push_back(w.data_ptr());
@@ -1456,9 +1369,7 @@ void conv_flip_multi(std::vector<Tensor> src, std::vector<Tensor> dst) {
 // one buffer; returns one channels_last [C, Cout, Rp, Sp] view per phase with taps, in phase
 // order (a, b) row-major (phases without taps are absent).
 std::vector<Tensor> conv_phase_weights(Tensor w, int64_t stride, int64_t pad) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && w.scalar_type() == torch::kBFloat16 &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_phase_weights: w must be a channels_last bf16 GPU tensor [Cout, C, R, S]");
+  check_nhwc_bf16(w, "conv_phase_weights: w", w.device());
   const int64_t Cout = w.size(0), C = w.size(1), R = w.size(2), S = w.size(3);
   TORCH_CHECK(Cout % 64 == 0 && C % 64 == 0 && stride >= 1 && pad >= 0,
               "conv_phase_weights: C and Cout must be multiples of 64");
@@ -1487,85 +1398,6 @@ std::vector<Tensor> conv_phase_weights(Tensor w, int64_t stride, int64_t pad) {
   return out;
 }
 
-// General NHWC convolution on the MFMA kernel (csrc/ops/conv_kernels.hip arena_conv_fwd_ex):
-// top/left padding, explicit output size, optional placement of the output pixels into a larger
-// preallocated tensor (y_out with y_map = [osh, osw, ooh, oow]: output (ho, wo) -> (ho*osh+ooh,
-// wo*osw+oow) of y_out; an optional 5th entry fill_sib = 1 also writes the untapped sibling pixels
-// of phase (0, 0) with the addend or zero), c16 mode (C == 16, S % 4 == 0). addend may alias y_out
-// (in-place accumulate: each element is read and written by the same lane).
-std::vector<Tensor> conv_fwd_ex(Tensor x, Tensor w, int64_t stride, int64_t pad_h, int64_t pad_w,
-                                int64_t Ho, int64_t Wo, int64_t variant, bool with_stats,
-                                OptT addend, OptT y_out, std::vector<int64_t> y_map, bool c16,
-                                bool stats_final) {
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 && w.scalar_type() == torch::kBFloat16 &&
-                  x.device() == w.device(),
-              "conv_fwd_ex: x and w must be 4-D bf16 tensors on one GPU");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  w.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_fwd_ex: x and w must be channels_last contiguous");
-  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int64_t Cout = w.size(0), R = w.size(2), S = w.size(3);
-  TORCH_CHECK(w.size(1) == C, "conv_fwd_ex: weight/input channel mismatch");
-  TORCH_CHECK(Cout % 64 == 0 && (c16 ? (C == 16 && S % 4 == 0) : C % 64 == 0),
-              "conv_fwd_ex: Cout % 64, and C % 64 (or C == 16, S % 4 == 0 in c16 mode)");
-  TORCH_CHECK(stride >= 1 && Ho >= 1 && Wo >= 1, "conv_fwd_ex: bad geometry");
-  TORCH_CHECK(N * Ho * Wo < (int64_t(1) << 31), "conv_fwd_ex: too many output pixels");
-  const ConvSplit ks = conv_split(x, variant, N * Ho * Wo, Cout, R * S * C);
-  Tensor y;
-  std::vector<int> map6;
-  if (y_out.has_value()) {
-    y = *y_out;
-    TORCH_CHECK(y.is_cuda() && y.device() == x.device() && y.dim() == 4 &&
-                    y.scalar_type() == torch::kBFloat16 && y.size(0) == N && y.size(1) == Cout &&
-                    y.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_fwd_ex: y_out must be a channels_last bf16 [N, Cout, Hy, Wy] tensor");
-    TORCH_CHECK((y_map.size() == 4 || y_map.size() == 5) && y_map[0] >= 1 && y_map[1] >= 1 &&
-                    y_map[2] >= 0 && y_map[3] >= 0 && (Ho - 1) * y_map[0] + y_map[2] < y.size(2) &&
-                    (Wo - 1) * y_map[1] + y_map[3] < y.size(3),
-                "conv_fwd_ex: y_map must place every output pixel inside y_out");
-    const bool fill = y_map.size() == 5 && y_map[4] != 0;
-    // sibling fill: phase (0, 0) whose pixels' siblings tile all of y_out
-    TORCH_CHECK(!fill || (y_map[2] == 0 && y_map[3] == 0 &&
-                          Ho == (y.size(2) + y_map[0] - 1) / y_map[0] &&
-                          Wo == (y.size(3) + y_map[1] - 1) / y_map[1]),
-                "conv_fwd_ex: fill_sib needs phase (0, 0) covering y_out");
-    map6 = {(int)y.size(2), (int)y.size(3), (int)y_map[0], (int)y_map[1], (int)y_map[2],
-            (int)y_map[3], fill ? 1 : 0};
-  } else {
-    y = torch::empty({N, Cout, Ho, Wo}, x.options().memory_format(at::MemoryFormat::ChannelsLast));
-  }
-  if (addend.has_value()) {
-    TORCH_CHECK(addend->sizes() == y.sizes() && addend->scalar_type() == torch::kBFloat16 &&
-                    addend->device() == y.device() &&
-                    addend->is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_fwd_ex: addend must be shaped like the output tensor");
-  }
-  const int rows = arena_conv_fwd_tile_rows(ks.base);
-  const int64_t m_tiles = (N * Ho * Wo + rows - 1) / rows;
-  TORCH_CHECK(!(with_stats && y_out.has_value()), "conv_fwd_ex: statistics need a dense output");
-  const bool fin = with_stats && stats_final;
-  TORCH_CHECK(!fin || (!addend.has_value() && Cout <= kAccC),
-              "conv_fwd_ex: stats_final is forward statistics without an addend");
-  Tensor part = with_stats && !fin
-                    ? torch::empty({m_tiles * 2 * Cout}, x.options().dtype(torch::kFloat32))
-                    : Tensor();
-  Tensor acc_t = fin ? bn_acc_set(x, Cout) : Tensor();
-  check_hip(arena_conv_fwd_ex(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                              with_stats && !fin ? part.data_ptr<float>() : nullptr,
-                              addend.has_value() ? addend->data_ptr() : nullptr, nullptr, nullptr,
-                              nullptr, nullptr, (int)N, (int)H, (int)W, (int)C, (int)Cout, (int)R,
-                              (int)S,
-                              (int)stride, (int)pad_h, (int)pad_w, (int)Ho, (int)Wo,
-                              y_out.has_value() ? map6.data() : nullptr, c16 ? 1 : 0,
-                              ks.base, fin ? acc_t.data_ptr<double>() : nullptr, ks.ks,
-                              ks.ks > 1 ? ks.ws.data_ptr() : nullptr, ks.cnt, cur_stream()),
-            "conv_fwd_ex");
-  if (fin) return {y, acc_t};
-  if (with_stats) return {y, part};
-  return {y};
-}
-
 // Every phase convolution of a stride-`stride` backward-data pass in one launch (v2 tile
 // `variant`): dy [N, C, H, W] (channels_last bf16), phase weights wps[p] [Cout, C, R_p, S_p]
 // (conv_phase_weights' views), geometry[p] = {pad_h, pad_w, Ho, Wo, ooh, oow}; phase p writes
@@ -1573,31 +1405,26 @@ std::vector<Tensor> conv_fwd_ex(Tensor x, Tensor w, int64_t stride, int64_t pad_
 // (+ addend shaped like dx_out, which may alias it).
 void conv_dgrad_phases(Tensor dy, std::vector<Tensor> wps, std::vector<std::vector<int64_t>> geom,
                        Tensor dx_out, OptT addend, int64_t stride, int64_t variant) {
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && dy.scalar_type() == torch::kBFloat16 &&
-                  dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad_phases: dy must be a channels_last bf16 GPU tensor");
+  const torch::Device dev = dy.device();
+  check_nhwc_bf16(dy, "conv_dgrad_phases: dy", dev);
   const int64_t np = (int64_t)wps.size();
   TORCH_CHECK(np >= 1 && np <= 4 && (int64_t)geom.size() == np, "conv_dgrad_phases: 1..4 phases");
   const int64_t N = dy.size(0), C = dy.size(1), H = dy.size(2), W = dy.size(3);
-  TORCH_CHECK(dx_out.is_cuda() && dx_out.device() == dy.device() && dx_out.dim() == 4 &&
-                  dx_out.scalar_type() == torch::kBFloat16 && dx_out.size(0) == N &&
-                  dx_out.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_dgrad_phases: dx_out must be a channels_last bf16 [N, Cout, Hy, Wy] tensor");
+  check_nhwc_bf16(dx_out, "conv_dgrad_phases: dx_out", dev);
+  TORCH_CHECK(dx_out.size(0) == N, "conv_dgrad_phases: dx_out must be [N, Cout, Hy, Wy]");
   const int64_t Cout = dx_out.size(1);
   if (addend.has_value()) {
-    TORCH_CHECK(addend->sizes() == dx_out.sizes() && addend->scalar_type() == torch::kBFloat16 &&
-                    addend->device() == dx_out.device() &&
-                    addend->is_contiguous(at::MemoryFormat::ChannelsLast),
+    check_nhwc_bf16(*addend, "conv_dgrad_phases: addend", dev);
+    TORCH_CHECK(addend->sizes() == dx_out.sizes(),
                 "conv_dgrad_phases: addend must be shaped like dx_out");
   }
   std::vector<const void*> wp(np);
   std::vector<int> R(np), S(np), ph(np), pw(np), Ho(np), Wo(np), oh(np), ow(np);
   for (int64_t p = 0; p < np; ++p) {
     const Tensor& w = wps[p];
-    TORCH_CHECK(w.is_cuda() && w.device() == dy.device() && w.dim() == 4 &&
-                    w.scalar_type() == torch::kBFloat16 && w.size(0) == Cout && w.size(1) == C &&
-                    w.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_dgrad_phases: phase weights must be channels_last bf16 [Cout, C, R, S]");
+    check_nhwc_bf16(w, "conv_dgrad_phases: phase weight", dev);
+    TORCH_CHECK(w.size(0) == Cout && w.size(1) == C,
+                "conv_dgrad_phases: phase weights must be [Cout, C, R, S]");
     TORCH_CHECK(geom[p].size() == 6, "conv_dgrad_phases: geometry is {pad_h, pad_w, Ho, Wo, ooh, oow}");
     wp[p] = w.data_ptr();
     R[p] = (int)w.size(2); S[p] = (int)w.size(3);
@@ -1615,62 +1442,6 @@ void conv_dgrad_phases(Tensor dy, std::vector<Tensor> wps, std::vector<std::vect
                                   R.data(), S.data(), ph.data(), pw.data(), Ho.data(), Wo.data(),
                                   oh.data(), ow.data(), (int)variant, cur_stream()),
             "conv_dgrad_phases");
-}
-
-// dW [Cout, C, R, S] (channels_last) of a convolution with top/left padding and an explicit
-// output size (dy's), c16 mode as conv_fwd_ex.
-// wgrad tile (Cout x R*S*C) of a variant: 0..3 (+4 serial) v1, 8..11 the v2 32x32x16 kernel
-static bool wgrad_tile(int64_t variant, int* tbm, int* tbn) {
-  static const int bm[4] = {128, 128, 64, 64}, bn[4] = {128, 64, 128, 64};
-  static const int bm2[7] = {128, 256, 128, 256, 128, 128, 128};
-  static const int bn2[7] = {128, 128, 256, 256, 128, 128, 128};
-  if (variant >= 0 && variant <= 7) {
-    *tbm = bm[variant & 3];
-    *tbn = bn[variant & 3];
-    return true;
-  }
-  if (variant >= 8 && variant <= 14) {
-    *tbm = bm2[variant - 8];
-    *tbn = bn2[variant - 8];
-    return true;
-  }
-  return false;
-}
-
-Tensor conv_wgrad_ex(Tensor x, Tensor dy, int64_t R, int64_t S, int64_t stride, int64_t pad_h,
-                     int64_t pad_w, int64_t variant, int64_t splits_hint, bool out_fp32,
-                     double scale, bool c16) {
-  TORCH_CHECK(x.is_cuda() && dy.is_cuda() && x.dim() == 4 && dy.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 && dy.scalar_type() == torch::kBFloat16 &&
-                  x.device() == dy.device(),
-              "conv_wgrad_ex: x and dy must be 4-D bf16 tensors on one GPU");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad_ex: x and dy must be channels_last contiguous");
-  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int64_t Cout = dy.size(1), Ho = dy.size(2), Wo = dy.size(3);
-  TORCH_CHECK(dy.size(0) == N && R >= 1 && S >= 1 && stride >= 1, "conv_wgrad_ex: bad geometry");
-  int tbm = 0, tbn = 0;
-  TORCH_CHECK(wgrad_tile(variant, &tbm, &tbn) && Cout % tbm == 0 &&
-                  (c16 ? (variant <= 7 && C == 16 && S % 4 == 0 && tbn == 64) : C % tbn == 0),
-              "conv_wgrad_ex: variant ", variant, " does not fit C=", C, " Cout=", Cout);
-  TORCH_CHECK(N * Ho * Wo < (int64_t(1) << 31), "conv_wgrad_ex: too many output pixels");
-  const int64_t Ktot = R * S * C;
-  const int splits = arena_conv_wgrad_splits((int)N, (int)Ho, (int)Wo, (int)Cout, (int)Ktot,
-                                             (int)variant, (int)splits_hint);
-  TORCH_CHECK(splits >= 1, "conv_wgrad_ex: bad split count");
-  Tensor ws = torch::empty({(int64_t)splits * Cout * Ktot}, x.options().dtype(torch::kFloat32));
-  Tensor dw = torch::empty({Cout, C, R, S}, x.options()
-                                                .dtype(out_fp32 ? torch::kFloat32 : torch::kBFloat16)
-                                                .memory_format(at::MemoryFormat::ChannelsLast));
-  check_hip(arena_conv_wgrad_ex(x.data_ptr(), dy.data_ptr(), ws.data_ptr<float>(),
-                                out_fp32 ? nullptr : dw.data_ptr(),
-                                out_fp32 ? dw.data_ptr<float>() : nullptr, (int)N, (int)H, (int)W,
-                                (int)C, (int)Cout, (int)R, (int)S, (int)stride, (int)pad_h,
-                                (int)pad_w, (int)Ho, (int)Wo, c16 ? 1 : 0, (int)variant,
-                                (int)splits_hint, (float)scale, cur_stream()),
-            "conv_wgrad_ex");
-  return dw;
 }
 
 // Space-to-depth of a channels_last [N, C<=4, H, W] bf16 image: [N, 16, H/2, W/2] (see kernel).
@@ -1733,27 +1504,31 @@ Tensor stem_weight_grad(Tensor dw16, Tensor w) {
 }
 
 // dW of an NHWC convolution: [Cout, C, R, S] channels_last, bf16 (for MasterSGD) or fp32.
-Tensor conv_wgrad(Tensor x, Tensor dy, int64_t R, int64_t S, int64_t stride, int64_t pad,
-                  int64_t variant, int64_t splits_hint, bool out_fp32, double scale) {
-  TORCH_CHECK(x.is_cuda() && dy.is_cuda() && x.dim() == 4 && dy.dim() == 4,
-              "conv_wgrad: x and dy must be 4-D GPU tensors");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && dy.scalar_type() == torch::kBFloat16,
-              "conv_wgrad: bfloat16 only");
-  TORCH_CHECK(x.device() == dy.device(), "conv_wgrad: x and dy on different devices");
-  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                  dy.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_wgrad: x and dy must be channels_last contiguous");
+// pad_h/pad_w: top/left padding. dy must have the output size of a convolution padded by them on
+// both sides, unless explicit_out: then the output size is dy's, whatever the padding (the stem's
+// space-to-depth form). c16 as in conv_fwd.
+Tensor conv_wgrad(Tensor x, Tensor dy, int64_t R, int64_t S, int64_t stride, int64_t pad_h,
+                  int64_t pad_w, int64_t variant, int64_t splits_hint, bool out_fp32, double scale,
+                  bool c16, bool explicit_out) {
+  check_nhwc_bf16(x, "conv_wgrad: x", x.device());
+  check_nhwc_bf16(dy, "conv_wgrad: dy", x.device());
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  const int64_t Cout = dy.size(1);
-  TORCH_CHECK(stride >= 1 && pad >= 0 && R >= 1 && S >= 1 && H + 2 * pad >= R && W + 2 * pad >= S,
-              "conv_wgrad: bad geometry");
-  const int64_t Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-  TORCH_CHECK(dy.size(0) == N && dy.size(2) == Ho && dy.size(3) == Wo,
-              "conv_wgrad: dy shape does not match the convolution geometry");
+  const int64_t Cout = dy.size(1), Ho = dy.size(2), Wo = dy.size(3);
+  TORCH_CHECK(dy.size(0) == N && R >= 1 && S >= 1 && stride >= 1, "conv_wgrad: bad geometry");
+  if (!explicit_out) {
+    TORCH_CHECK(pad_h >= 0 && pad_w >= 0 && H + 2 * pad_h >= R && W + 2 * pad_w >= S,
+                "conv_wgrad: bad geometry");
+    TORCH_CHECK(Ho == (H + 2 * pad_h - R) / stride + 1 && Wo == (W + 2 * pad_w - S) / stride + 1,
+                "conv_wgrad: dy shape does not match the convolution geometry");
+  }
   int tbm = 0, tbn = 0;
-  TORCH_CHECK(wgrad_tile(variant, &tbm, &tbn), "conv_wgrad: variant must be 0..14");
-  TORCH_CHECK(C % tbn == 0 && Cout % tbm == 0, "conv_wgrad: variant ", variant, " needs C % ",
-              tbn, " == 0 and Cout % ", tbm, " == 0");
+  TORCH_CHECK(variant == (int)variant && arena_conv_wgrad_tile((int)variant, &tbm, &tbn),
+              "conv_wgrad: unknown variant ", variant);
+  TORCH_CHECK(Cout % tbm == 0 &&
+                  (c16 ? (variant <= 7 && C == 16 && S % 4 == 0 && tbn == 64) : C % tbn == 0),
+              "conv_wgrad: variant ", variant, " needs C % ", tbn, " == 0 and Cout % ", tbm,
+              " == 0 (c16 mode: a 64-wide v1 tile, C == 16, S % 4 == 0); C = ", C, ", Cout = ",
+              Cout);
   TORCH_CHECK(N * Ho * Wo < (int64_t(1) << 31), "conv_wgrad: too many output pixels");
   const int64_t Ktot = R * S * C;
   const int splits = arena_conv_wgrad_splits((int)N, (int)Ho, (int)Wo, (int)Cout, (int)Ktot,
@@ -1766,9 +1541,9 @@ Tensor conv_wgrad(Tensor x, Tensor dy, int64_t R, int64_t S, int64_t stride, int
   check_hip(arena_conv_wgrad_ex(x.data_ptr(), dy.data_ptr(), ws.data_ptr<float>(),
                                 out_fp32 ? nullptr : dw.data_ptr(),
                                 out_fp32 ? dw.data_ptr<float>() : nullptr, (int)N, (int)H, (int)W,
-                                (int)C, (int)Cout, (int)R, (int)S, (int)stride, (int)pad, (int)pad,
-                                0, 0, 0, (int)variant, (int)splits_hint, (float)scale,
-                                cur_stream()),
+                                (int)C, (int)Cout, (int)R, (int)S, (int)stride, (int)pad_h,
+                                (int)pad_w, (int)Ho, (int)Wo, c16 ? 1 : 0, (int)variant,
+                                (int)splits_hint, (float)scale, cur_stream()),
             "conv_wgrad");
   return dw;
 }
@@ -1888,6 +1663,7 @@ Tensor gap_bwd(Tensor g, int64_t H, int64_t W) {
   return dx;
 }
 
+// Returns (y, pos): pos = uint8 in-window argmax, same NHWC layout as y.
 std::vector<Tensor> maxpool_fwd(Tensor x, int64_t k, int64_t s, int64_t p) {
   pool_check(x, "x");
   const int N = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
@@ -2072,11 +1848,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_flip_weight", &conv_flip_weight);
   m.def("conv_flip_multi", &conv_flip_multi);
   m.def("conv_phase_weights", &conv_phase_weights);
-  m.def("conv_fwd_ex", &conv_fwd_ex, py::arg("x"), py::arg("w"), py::arg("stride"),
-        py::arg("pad_h"), py::arg("pad_w"), py::arg("Ho"), py::arg("Wo"), py::arg("variant"),
-        py::arg("with_stats"), py::arg("addend"), py::arg("y_out"), py::arg("y_map"),
-        py::arg("c16"), py::arg("stats_final") = false);
-  m.def("conv_wgrad_ex", &conv_wgrad_ex);
   m.def("conv_dgrad_phases", &conv_dgrad_phases, py::arg("dy"), py::arg("wps"), py::arg("geom"),
         py::arg("dx_out"), py::arg("addend"), py::arg("stride"), py::arg("variant"));
   m.def("s2d_stem", &s2d_stem);
@@ -2088,14 +1859,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("acc_b") = py::none(), py::arg("zero_f") = py::none(),
         py::arg("acc_ready") = false, py::arg("x2") = py::none(),
         py::arg("mean2") = py::none(), py::arg("acc2") = py::none());
-  m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"),
-        py::arg("variant"), py::arg("with_stats"), py::arg("addend") = py::none(),
+  m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad_h"),
+        py::arg("pad_w"), py::arg("Ho"), py::arg("Wo"), py::arg("variant"),
+        py::arg("with_stats"), py::arg("addend") = py::none(), py::arg("addmask") = py::none(),
         py::arg("bn_x") = py::none(), py::arg("bn_mask") = py::none(),
-        py::arg("bn_mean") = py::none(), py::arg("addmask") = py::none(),
-        py::arg("stats_final") = false, py::arg("bn_acc") = py::none());
+        py::arg("bn_mean") = py::none(), py::arg("bn_acc") = py::none(),
+        py::arg("stats_final") = false, py::arg("y_out") = py::none(),
+        py::arg("y_map") = std::vector<int64_t>{}, py::arg("c16") = false);
   m.def("conv_wgrad", &conv_wgrad, py::arg("x"), py::arg("dy"), py::arg("R"), py::arg("S"),
-        py::arg("stride"), py::arg("pad"), py::arg("variant"), py::arg("splits_hint"),
-        py::arg("out_fp32"), py::arg("scale"));
+        py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"), py::arg("variant"),
+        py::arg("splits_hint"), py::arg("out_fp32"), py::arg("scale"), py::arg("c16") = false,
+        py::arg("explicit_out") = false);
+  // the kernels' tile tables (arena_amd/ops/conv.py keeps a copy that the tests check against)
+  m.def("conv_tile", [](int64_t code) {
+    int bm = 0, bn = 0;
+    TORCH_CHECK(code == (int)code && arena_conv_tile((int)code, &bm, &bn),
+                "conv_tile: unknown variant code ", code);
+    return std::make_pair(bm, bn);
+  });
+  m.def("conv_wgrad_tile", [](int64_t code) {
+    int bm = 0, bn = 0;
+    TORCH_CHECK(code == (int)code && arena_conv_wgrad_tile((int)code, &bm, &bn),
+                "conv_wgrad_tile: unknown variant code ", code);
+    return std::make_pair(bm, bn);
+  });
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("xent_fwd", &xent_fwd);
   m.def("xent_bwd", &xent_bwd);

@@ -1807,9 +1807,11 @@ hipError_t launch2_t(const ConvArgs& a0, hipStream_t st) {
   return hipGetLastError();
 }
 
-// v2 variant table (code 1024 + index): BM x BN tile, waves NWM x NWN, stage buffers
-constexpr int kV2Base = 4096;   // above every v1 code (base + 16 (k - 1), split-K k <= 16)
-constexpr int kV2Count = 19;
+// variant codes (abi.h): v1 tile + kV1Tiles (k - 1) with split-K k <= 16, v2 tile kV2Base + index
+constexpr int kV1Tiles = ARENA_CONV_V1_TILES;
+constexpr int kV2Base = ARENA_CONV_V2_BASE;   // above every v1 code
+constexpr int kV2Count = ARENA_CONV_V2_COUNT;
+// v2 variant table: BM x BN tile (launch2: waves NWM x NWN, stage buffers)
 constexpr int kV2Tiles[kV2Count][2] = {{256, 128}, {256, 256}, {128, 128}, {256, 64}, {128, 256},
                                        {128, 64}, {64, 64}, {64, 128},
                                        {128, 128}, {128, 64}, {64, 128}, {64, 64},
@@ -1947,7 +1949,7 @@ hipError_t arena_conv_fwd_ex(const void* x, const void* w, void* y, float* part,
   a.M = (int)M;
   a.Ktot = R * S * C;
   const bool v2 = variant >= kV2Base && variant < kV2Base + kV2Count;
-  if (!v2 && (variant < 0 || variant > 15)) return hipErrorInvalidValue;
+  if (!v2 && (variant < 0 || variant >= kV1Tiles)) return hipErrorInvalidValue;
   if (!c16) {   // descriptor staging: 31-bit byte offsets, a 32-bit tap mask
     const long long xb = (long long)N * H * W * C * 2, wb = (long long)Cout * a.Ktot * 2;
     if (xb >= (1LL << 31) || wb >= (1LL << 31) || R * S > 32) return hipErrorInvalidValue;
@@ -2030,49 +2032,43 @@ hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N,
   return launch2(a, idx, st);
 }
 
-hipError_t arena_conv_fwd(const void* x, const void* w, void* y, float* part, const void* add,
-                          const void* bnx, const uint8_t* bnmask, const float* bnmean,
-                          int N, int H, int W, int C, int Cout, int R, int S, int stride, int pad,
-                          int variant, hipStream_t st) {
-  return arena_conv_fwd_ex(x, w, y, part, add, nullptr, bnx, bnmask, bnmean, N, H, W, C, Cout, R, S,
-                           stride, pad, pad, 0, 0, nullptr, 0, variant, nullptr, 1, nullptr, nullptr,
-                           st);
-}
-
-// Split-K workspace of one launch, in floats (0 when ksplit == 1), and its ticket count (tiles).
-static void conv_tile(int variant, int* bm, int* bn) {
+// The BM x BN output tile of a variant code (abi.h; a v1 code may carry its split-K factor):
+// returns 0 for a code no kernel has.
+int arena_conv_tile(int variant, int* bm, int* bn) {
   static const int tm[4] = {128, 128, 64, 64}, tn[4] = {128, 64, 128, 64};
   if (variant >= kV2Base && variant < kV2Base + kV2Count) {
     *bm = kV2Tiles[variant - kV2Base][0];
     *bn = kV2Tiles[variant - kV2Base][1];
-  } else if (variant >= 12) {
+    return 1;
+  }
+  if (variant < 0 || variant >= ARENA_CONV_V1_END) return 0;
+  variant %= kV1Tiles;
+  if (variant >= 12) {
     *bm = 256;
     *bn = (variant & 1) ? 64 : 128;
   } else {
     *bm = tm[variant & 3];
     *bn = tn[variant & 3];
   }
+  return 1;
 }
 
+// Split-K workspace of one launch, in floats (0 when ksplit == 1), and its ticket count (tiles).
 long long arena_conv_fwd_ksplit_floats(long long M, int Cout, int variant, int ksplit) {
-  if (ksplit <= 1 || variant < 0 || variant > 15) return 0;   // split-K: the v1 tiles only
-  int bm, bn;
-  conv_tile(variant, &bm, &bn);
+  int bm, bn;   // split-K: the v1 tiles only
+  if (ksplit <= 1 || variant >= kV1Tiles || !arena_conv_tile(variant, &bm, &bn)) return 0;
   return ((M + bm - 1) / bm) * (Cout / bn) * ksplit * bm * bn;
 }
 
 long long arena_conv_fwd_tiles(long long M, int Cout, int variant) {
-  if (variant < 0 || (variant > 15 && !(variant >= kV2Base && variant < kV2Base + kV2Count)))
-    return 0;
   int bm, bn;
-  conv_tile(variant, &bm, &bn);
+  if ((variant >= kV1Tiles && variant < kV2Base) || !arena_conv_tile(variant, &bm, &bn)) return 0;
   return ((M + bm - 1) / bm) * (Cout / bn);
 }
 
 int arena_conv_fwd_tile_rows(int variant) {
   int bm, bn;
-  conv_tile(variant, &bm, &bn);
-  return bm;
+  return arena_conv_tile(variant, &bm, &bn) ? bm : 0;
 }
 
 }  // extern "C"
@@ -3081,13 +3077,21 @@ hipError_t launch_wgrad(WgradArgs a, int splits_hint, bool serial, hipStream_t s
 extern "C" {
 
 
+// The Cout x R*S*C tile of a weight-gradient variant (0..3, + 4 serial: v1; 8..: the v2 kernel's
+// kWg2Tiles): returns 0 for a code no kernel has.
+int arena_conv_wgrad_tile(int variant, int* bm, int* bn) {
+  static const int tm[4] = {128, 128, 64, 64}, tn[4] = {128, 64, 128, 64};
+  if (variant < 0 || variant >= 8 + kWg2Count) return 0;
+  *bm = variant >= 8 ? kWg2Tiles[variant - 8][0] : tm[variant & 3];
+  *bn = variant >= 8 ? kWg2Tiles[variant - 8][1] : tn[variant & 3];
+  return 1;
+}
+
 // Number of split slabs the wgrad launch will use (the caller sizes the workspace with it).
 int arena_conv_wgrad_splits(int N, int Ho, int Wo, int Cout, int Ktot, int variant,
                             int splits_hint) {
-  static const int bm[4] = {128, 128, 64, 64}, bn[4] = {128, 64, 128, 64};
-  if (variant < 0 || variant >= 8 + kWg2Count) return -1;
-  const int tbm = variant >= 8 ? kWg2Tiles[variant - 8][0] : bm[variant & 3];
-  const int tbn = variant >= 8 ? kWg2Tiles[variant - 8][1] : bn[variant & 3];
+  int tbm, tbn;
+  if (!arena_conv_wgrad_tile(variant, &tbm, &tbn)) return -1;
   const int tiles = (Cout / tbm) * (Ktot / tbn);
   const long long M = (long long)N * Ho * Wo;
   const int total = (int)((M + 63) / 64);
@@ -3105,13 +3109,11 @@ hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* d
                                float* dw_f32, int N, int H, int W, int C, int Cout, int R, int S,
                                int stride, int pad_h, int pad_w, int Ho, int Wo, int c16,
                                int variant, int splits_hint, float scale, hipStream_t st) {
-  static const int bm[4] = {128, 128, 64, 64}, bn[4] = {128, 64, 128, 64};
-  if (variant < 0 || variant >= 8 + kWg2Count) return hipErrorInvalidValue;
+  int tbm, tbn;
+  if (!arena_conv_wgrad_tile(variant, &tbm, &tbn)) return hipErrorInvalidValue;
   const bool v2 = variant >= 8;
   const int tv = variant & 3;
   const bool serial = !v2 && variant >= 4;
-  const int tbm = v2 ? kWg2Tiles[variant - 8][0] : bm[tv];
-  const int tbn = v2 ? kWg2Tiles[variant - 8][1] : bn[tv];
   if (v2 && c16) return hipErrorInvalidValue;
   if (c16 ? (C != 16 || S % 4 || tbn != 64) : (C % tbn != 0)) return hipErrorInvalidValue;
   if (Cout % tbm || N <= 0 || stride <= 0) return hipErrorInvalidValue;
@@ -3171,13 +3173,6 @@ hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* d
                        dim3(256), 0, st, reinterpret_cast<const float4*>(ws), splits, n4,
                        reinterpret_cast<uint2*>(dw_bf16), reinterpret_cast<float4*>(dw_f32), scale);
   return hipGetLastError();
-}
-
-hipError_t arena_conv_wgrad(const void* x, const void* dy, float* ws, void* dw_bf16, float* dw_f32,
-                            int N, int H, int W, int C, int Cout, int R, int S, int stride,
-                            int pad, int variant, int splits_hint, float scale, hipStream_t st) {
-  return arena_conv_wgrad_ex(x, dy, ws, dw_bf16, dw_f32, N, H, W, C, Cout, R, S, stride, pad, pad,
-                             0, 0, 0, variant, splits_hint, scale, st);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "abi.h"
+
 namespace {
 
 constexpr int kT = 256;

@@ -329,15 +329,102 @@ def test_conv_kernel_rejects_bad_shapes():
     from arena_amd.ops import _ext
     x, wt = _data(1, 32, 8, 8, 64, 3, "cuda")
     with pytest.raises(RuntimeError, match="multiples of 64"):
-        _ext.load().conv_fwd(x, wt, 1, 1, 1, False)
+        _ext.load().conv_fwd(x, wt, 1, 1, 1, 0, 0, 1, False)
     x, wt = _data(1, 64, 8, 8, 64, 3, "cuda")
     with pytest.raises(RuntimeError, match="Cout % 128"):
-        _ext.load().conv_fwd(x, wt, 1, 1, 0, False)
+        _ext.load().conv_fwd(x, wt, 1, 1, 1, 0, 0, 0, False)
     # pad > R-1 would need a negative backward-data padding: not a kernel shape (MIOpen runs it)
     x, wt = _data(2, 64, 8, 8, 128, 1, "cuda")
     assert conv.kernel_ok(x, wt, 1, 0) and not conv.kernel_ok(x, wt, 1, 1)
     x3, w3 = _data(2, 64, 8, 8, 128, 3, "cuda")
     assert conv.kernel_ok(x3, w3, 1, 2) and not conv.kernel_ok(x3, w3, 1, 3)
+
+
+@pytest.mark.gpu
+def test_python_tile_tables_match_the_kernels():
+    """conv.TILES / conv.WGRAD_TILES are copies (the planner and the CPU tests use them without
+    the extension) of the tables in conv_kernels.hip: every code, split-K codes included, maps to
+    the same tile, and codes next to the tables' ends are unknown to both. Launches nothing."""
+    from arena_amd.ops import _ext
+    ext = _ext.load()
+    for code, tile in conv.TILES.items():
+        assert ext.conv_tile(code) == tile, code
+    for code, tile in conv.WGRAD_TILES.items():
+        assert ext.conv_wgrad_tile(code) == tile, code
+    for bad in (conv.V2 + len(conv.V2_TILES), -1, 256):
+        assert bad not in conv.TILES
+        with pytest.raises(RuntimeError, match="unknown variant"):
+            ext.conv_tile(bad)
+    assert 15 not in conv.WGRAD_TILES
+    with pytest.raises(RuntimeError, match="unknown variant"):
+        ext.conv_wgrad_tile(15)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", [3, conv.V2 + 6])
+def test_conv_fwd_derived_and_explicit_output_size_agree(variant):
+    """The one forward binding: Ho = Wo = 0 (derive from the symmetric padding) and the explicit
+    output size of the same convolution run the same launch."""
+    from arena_amd.ops import _ext
+    ext = _ext.load()
+    x, wt = _data(2, 64, 8, 8, 64, 3, "cuda")
+    (y0,) = ext.conv_fwd(x, wt, 1, 1, 1, 0, 0, variant, False)
+    (y1,) = ext.conv_fwd(x, wt, 1, 1, 1, 8, 8, variant, False)
+    assert y0.shape == (2, 64, 8, 8) and torch.equal(y0, y1)
+    ref = F.conv2d(x.float(), wt.float(), padding=1)
+    assert _rel(y0, ref) < 1e-2
+
+
+# variant 8 (the v2 kernel's 128 x 128 tile) needs 128 channels on both sides; variant 3 runs on
+# both shapes
+@pytest.mark.gpu
+@pytest.mark.parametrize("ch,variant", [(64, 3), (128, 3), (128, 8)])
+def test_conv_wgrad_with_and_without_explicit_out_agree(ch, variant):
+    """The one weight-gradient binding: with explicit_out the output size is dy's, without it dy
+    must match the symmetric-padding geometry; on a dy that does, both are the same launch."""
+    from arena_amd.ops import _ext
+    ext = _ext.load()
+    x, _ = _data(2, ch, 8, 8, ch, 3, "cuda")
+    dy, _ = _data(2, ch, 8, 8, ch, 3, "cuda", seed=1)
+    args = (3, 3, 1, 1, 1, variant, 0, True, 1.0)
+    dw0 = ext.conv_wgrad(x, dy, *args)
+    dw1 = ext.conv_wgrad(x, dy, *args, explicit_out=True)
+    assert dw0.shape == (ch, ch, 3, 3) and torch.equal(dw0, dw1)
+    dw_ref = torch.ops.aten.convolution_backward(
+        dy.float(), x.float(), torch.empty(ch, ch, 3, 3, device="cuda"), None, [1, 1], [1, 1],
+        [1, 1], False, [0, 0], 1, [False, True, False])[1]
+    assert _rel(dw0, dw_ref) < 5e-3
+    short = dy[:, :, :7].contiguous(memory_format=torch.channels_last)
+    with pytest.raises(RuntimeError, match="does not match the convolution geometry"):
+        ext.conv_wgrad(x, short, *args)
+
+
+@pytest.mark.gpu
+def test_conv_fwd_rejects_combinations_without_a_kernel():
+    """Argument combinations the two old forward bindings could not express are refused on the
+    host, before any launch (y_out keeps its contents)."""
+    from arena_amd.ops import _ext
+    ext = _ext.load()
+    x, wt = _data(2, 64, 8, 8, 64, 3, "cuda")
+    y_out = torch.full_like(x, 3.0)
+    bn_mean = torch.zeros(64, device="cuda")
+    bits = torch.zeros(x.numel() // 8, device="cuda", dtype=torch.uint8)
+    geo = (x, wt, 1, 1, 1, 8, 8, 3)
+    with pytest.raises(RuntimeError, match="statistics need a dense output"):
+        ext.conv_fwd(*geo, True, y_out=y_out, y_map=[1, 1, 0, 0])
+    with pytest.raises(RuntimeError, match="statistics need a dense output"):
+        ext.conv_fwd(*geo, True, stats_final=True, y_out=y_out, y_map=[1, 1, 0, 0])
+    with pytest.raises(RuntimeError, match="bn_x form"):
+        ext.conv_fwd(*geo, False, bn_x=x, bn_mean=bn_mean, y_out=y_out, y_map=[1, 1, 0, 0])
+    with pytest.raises(RuntimeError, match="addmask needs an addend"):
+        ext.conv_fwd(*geo, False, addmask=bits)
+    with pytest.raises(RuntimeError, match="bn_x form"):
+        ext.conv_fwd(*geo, True, bn_x=x, bn_mean=bn_mean, c16=True)
+    with pytest.raises(RuntimeError, match="bn_acc is the bn_x form's"):
+        ext.conv_fwd(*geo, True, bn_acc=torch.zeros(ext.acc_rep, 2, 64, device="cuda",
+                                                    dtype=torch.float64))
+    torch.cuda.synchronize()
+    assert bool((y_out == 3.0).all())
 
 
 @pytest.mark.gpu

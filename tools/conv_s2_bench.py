@@ -68,8 +68,8 @@ def main():
     res["ours_s2d_us"] = round(timeit(lambda: ext.s2d_stem(x), args.reps), 1)
     res["ours_weight_prep_us"] = round(timeit(lambda: conv.stem_weight(wb), args.reps), 1)
     for v in [v for v in conv.variants_for(64) if conv.TILES[v][1] == 64]:
-        res[f"ours_fwd_v{v}_us"] = round(timeit(lambda: ext.conv_fwd_ex(
-            z, w16, 1, 2, 2, 112, 112, v, True, None, None, [], True), args.reps), 1)
+        res[f"ours_fwd_v{v}_us"] = round(timeit(lambda: ext.conv_fwd(
+            z, w16, 1, 2, 2, 112, 112, v, True, c16=True), args.reps), 1)
     y = F.conv2d(x, wb, stride=2, padding=3)
     dy = torch.randn_like(y)
     res["miopen_wgrad_us"] = round(timeit(lambda: torch.ops.aten.convolution_backward(
@@ -77,8 +77,9 @@ def main():
         args.reps), 1)
     for v in (3, 7):
         for sp in (0, 64, 128, 256):
-            res[f"ours_wgrad_v{v}_s{sp}_us"] = round(timeit(lambda: ext.conv_wgrad_ex(
-                z, dy, 4, 4, 1, 2, 2, v, sp, False, 1.0, True), args.reps), 1)
+            res[f"ours_wgrad_v{v}_s{sp}_us"] = round(timeit(lambda: ext.conv_wgrad(
+                z, dy, 4, 4, 1, 2, 2, v, sp, False, 1.0, c16=True, explicit_out=True),
+                args.reps), 1)
     print(json.dumps(res), flush=True)
     print(json.dumps({"dgrad_s2_total_us": {k: round(v, 1) for k, v in tot.items()}}), flush=True)
 
