@@ -25,87 +25,15 @@ import torch
 from . import _ext, planstore
 
 Tensor = torch.Tensor
-TILES = {0: (128, 128), 1: (128, 64), 2: (64, 128), 3: (64, 64)}
-# + 4: four-stage K pipeline (3 steps in flight); + 8: single stage buffer, serial K loop, high
-# occupancy
-TILES.update({v + d: t for v, t in list(TILES.items()) for d in (4, 8)})
-# 12 / 13: 256x128 / 256x64 tiles on 8 waves, two stage buffers; 14 / 15: three
-TILES.update({12: (256, 128), 13: (256, 64), 14: (256, 128), 15: (256, 64)})
-# + 16 * (k - 1): the same tile with its K steps split over k blocks (in-kernel ticket reduction,
-# bit-reproducible): for the layers whose tile count leaves CUs idle (14x14 / 7x7 at batch 128)
-KSPLITS = (2, 3, 4, 6, 8)
-TILES.update({v + 16 * (k - 1): TILES[v] for v in range(16) for k in KSPLITS})
-# 4096 + i: the v2 tile kernel (conv_kernels.hip conv2_body): 32x32x16 MFMAs, 8-wave 256-row
-# tiles (4-wave 128x128), two K steps in flight, epilogue through an fp32 LDS tile. Forward and
-# backward-data (incl. the strided phases): plain, masked addend, BatchNorm statistics, BatchNorm-
-# backward partials or sums (BNGradLink).
-V2 = 4096
-V2_TILES = {V2 + 0: (256, 128), V2 + 1: (256, 256), V2 + 2: (128, 128), V2 + 3: (256, 64),
-            V2 + 4: (128, 256), V2 + 5: (128, 64), V2 + 6: (64, 64), V2 + 7: (64, 128),
-            # serial single-buffer forms with wave-row epilogue bands: 4 waves per SIMD
-            V2 + 8: (128, 128), V2 + 9: (128, 64), V2 + 10: (64, 128), V2 + 11: (64, 64)}
-# 3x3 / stride 1 / pad 1 halo forms (width <= 63): the tile's input window is staged once per
-# 64-channel chunk and the nine taps read it shifted (conv_kernels.hip Conv2Geo::HALO)
-V2_HALO = {V2 + 12: (128, 128), V2 + 13: (128, 64),
-           V2 + 14: (128, 64),   # 14: the window of <= 31-wide images (four blocks per CU)
-           # 15: two groups of four waves split the 64-channel chunks (two waves per SIMD; even
-           # chunk counts only)
-           V2 + 15: (128, 128),
-           # 16..18: eight waves, a 256-pixel or 256-channel tile per block (each weight tap
-           # staged into LDS feeds twice the MFMAs of a 128x128 tile)
-           V2 + 16: (256, 128), V2 + 17: (128, 256), V2 + 18: (256, 64)}
-HALO_MAX_W = 63
-HALO_SMALL = {V2 + v: 31 for v in (14, 15)}
-HALO_SPLIT2 = {V2 + 15}
-HALO_WIDE = {V2 + v for v in range(16, 19)}   # the 8-wave forms (set_halo_wide, for A/Bs)
-_HALO_WIDE_ON = True
-V2_TILES.update(V2_HALO)
-TILES.update(V2_TILES)
-_V2_ON = os.environ.get("ARENA_CONV_V2", "1") != "0"
-_CUS = 256
-
-
-def kvariant(v: int, ks: int) -> int:
-    """Variant code of tile variant ``v`` (0..15) with its K steps split over ``ks`` blocks."""
-    return v + 16 * (ks - 1)
-
-
-def split_of(v: int) -> int:
-    return 1 if v >= V2 else v // 16 + 1
-
-
-def set_v2(on: bool) -> None:
-    """A/B switch: offer the v2 tile kernel to the autotuner (part of the plan key)."""
-    global _V2_ON
-    _V2_ON = bool(on)
-
-
-def v2_variants_for(cout: int):
-    """v2 tile variants for ``cout`` output channels (forward / backward-data, incl. the strided
-    phases); the halo forms come from ``halo_variants_for``."""
-    return [v for v, (_, bn) in V2_TILES.items()
-            if cout % bn == 0 and v not in V2_HALO] if _V2_ON else []
-
-
-def set_halo_wide(on: bool) -> None:
-    """A/B switch: offer the 8-wave halo forms to the autotuner (part of the plan key)."""
-    global _HALO_WIDE_ON
-    _HALO_WIDE_ON = bool(on)
-
-
-def halo_variants_for(cout: int, k, stride: int, pad: int, width: int, cin: int | None = None):
-    """The 3x3 halo forms, for a 3x3 / stride 1 / pad 1 convolution of a <= 63-wide image
-    (``cin``: the input channels; the two-group forms need an even number of 64-channel chunks)."""
-    if not _V2_ON or tuple(k) != (3, 3) or stride != 1 or pad != 1 or width > HALO_MAX_W:
-        return []
-    return [v for v, (_, bn) in V2_HALO.items()
-            if cout % bn == 0 and width <= HALO_SMALL.get(v, HALO_MAX_W)
-            and (v not in HALO_SPLIT2 or (cin is None or (cin // 64) % 2 == 0))
-            and (_HALO_WIDE_ON or v not in HALO_WIDE)]
-
-
-def out_hw(h: int, w: int, r: int, s: int, stride: int, pad: int) -> Tuple[int, int]:
-    return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+# the variant tables and everything that reasons about variant codes: conv_variants.py (pure
+# Python); re-exported here for the callers of conv.TILES, conv.variants_for(...) and the rest
+from . import conv_variants as cv
+from .conv_variants import (FWD, HALO_MAX_W, HALO_SMALL, HALO_SPLIT2, HALO_WIDE,  # noqa: F401
+                            KSPLITS, TILES, V2, V2_HALO, V2_TILES, WGRAD, WGRAD_GROUPS,
+                            WGRAD_TILES, WGRAD_V2, _CUS, _WGRAD_BPC, _wgrad_candidates,
+                            fwd_variant, halo_variants_for, kvariant, out_hw, pick_variant,
+                            plan_candidates, set_halo_wide, set_v2, split_of, split_variants_for,
+                            v2_variants_for, variants_for, wgrad_variants_for)
 
 
 def kernel_ok(x: Tensor, w: Tensor, stride: int, pad: int) -> bool:
@@ -115,51 +43,6 @@ def kernel_ok(x: Tensor, w: Tensor, stride: int, pad: int) -> bool:
             # the stride-1 backward-data pass is a conv with padding R-1-pad: never negative
             and pad <= min(w.shape[2], w.shape[3]) - 1
             and x.shape[2] + 2 * pad >= w.shape[2] and x.shape[3] + 2 * pad >= w.shape[3])
-
-
-def variants_for(cout: int):
-    """Unsplit tile variants for ``cout`` output channels."""
-    return [v for v, (_, bn) in TILES.items() if v < 16 and cout % bn == 0]
-
-
-def split_variants_for(m: int, cout: int, ktot: int):
-    """Split-K candidates for a GEMM of ``m`` rows, ``cout`` columns and ``ktot`` reduction: for
-    tiles whose grid gives fewer than two blocks per CU, the splits that bring it to about 2 or 4
-    blocks per CU with at least 4 K steps per slice."""
-    out = []
-    if os.environ.get("ARENA_CONV_KSPLIT", "1") == "0":
-        return out
-    steps = ktot // 64
-    for v in variants_for(cout):
-        if 4 <= v < 8 or v >= 14:
-            continue   # the deep pipelines need long K loops: not split candidates
-        bm, bn = TILES[v]
-        tiles = -(-m // bm) * (cout // bn)
-        if tiles >= 2 * _CUS or tiles > 65536:
-            continue
-        ks_set = set()
-        for want in (2 * _CUS, 4 * _CUS):
-            need = -(-want // tiles)
-            ks = next((k for k in KSPLITS if k >= need), KSPLITS[-1])
-            if steps // ks >= 4:
-                ks_set.add(ks)
-        out += [kvariant(v, k) for k in sorted(ks_set)]
-    return out
-
-
-def pick_variant(m: int, cout: int) -> int:
-    """Largest tile that still gives every CU at least two blocks; else the most blocks."""
-    best, best_blocks = None, 0
-    for v in (0, 1, 2, 3):
-        bm, bn = TILES[v]
-        if cout % bn:
-            continue
-        blocks = -(-m // bm) * (cout // bn)
-        if blocks >= 2 * _CUS:
-            return v
-        if blocks > best_blocks:
-            best, best_blocks = v, blocks
-    return best
 
 
 def conv2d_fwd(x: Tensor, w: Tensor, stride: int = 1, pad: int = 0, variant: int = -1,
@@ -354,7 +237,7 @@ def conv2d_bwd_data_strided(dy: Tensor, w: Tensor, x_hw: Tuple[int, int], stride
         Hp, Wp = (H - a + stride - 1) // stride, (W - b + stride - 1) // stride
         if Hp > 0 and Wp > 0:
             geo.append((wp, [Rp - 1 - ca, Sp - 1 - cb, Hp, Wp, a, b]))
-    if V2 <= variant and variant not in V2_HALO and len(geo) > 1:
+    if variant in FWD and FWD[variant].phases and len(geo) > 1:
         # v2 tiles: every phase in one launch (the phases' tiles fill the chip together)
         ext.conv_dgrad_phases(dy, [g[0] for g in geo], [g[1] for g in geo], dx, addend, stride,
                               int(variant))
@@ -571,23 +454,6 @@ class GradJoin:
         return False
 
 
-WGRAD_TILES = {0: (128, 128), 1: (128, 64), 2: (64, 128), 3: (64, 64)}   # Cout x R*S*C
-WGRAD_TILES.update({v + 4: t for v, t in list(WGRAD_TILES.items())})   # + 4: serial
-# 8..11: the v2 weight-gradient kernel (32x32x16 MFMAs, 128/256-wide tiles, two steps in flight)
-WGRAD_V2 = {8: (128, 128), 9: (256, 128), 10: (128, 256), 11: (256, 256),
-            12: (128, 128),   # 12: serial single-buffer, four waves per SIMD
-            # 13 / 14: 12 with two / four wave groups per block splitting its pixel steps (the
-            # same waves per CU in 1/2 / 1/4 of the blocks: that many fewer fp32 split slabs)
-            13: (128, 128), 14: (128, 128)}
-WGRAD_GROUPS = {13: 2, 14: 4}
-WGRAD_TILES.update(WGRAD_V2)
-
-
-def wgrad_variants_for(cin: int, cout: int):
-    return [v for v, (bm, bn) in WGRAD_TILES.items() if cout % bm == 0 and cin % bn == 0
-            and (v < 8 or _V2_ON)]
-
-
 def conv2d_wgrad(x: Tensor, dy: Tensor, kernel: Tuple[int, int], stride: int = 1, pad: int = 0,
                  variant: int = -1, splits: int = 0, out_dtype=torch.bfloat16,
                  scale: float = 1.0) -> Tensor:
@@ -682,24 +548,6 @@ def _miopen_bwd(dy, x, w, stride, pad, mask):
                                                [1, 1], False, [0, 0], 1, mask)
 
 
-# blocks per CU the weight-gradient split counts aim at (ARENA_WGRAD_BPC, for A/Bs)
-_WGRAD_BPC = tuple(float(b) for b in os.environ.get("ARENA_WGRAD_BPC", "1,2,4").split(","))
-
-
-def _wgrad_candidates(cin, cout, k):
-    """(tile variant, split count) pairs: splits that give ~1, 2 or 4 blocks per CU."""
-    out = []
-    for v in wgrad_variants_for(cin, cout):
-        bm, bn = WGRAD_TILES[v]
-        tiles = (cout // bm) * (k[0] * k[1] * cin // bn)
-        # wave-group forms: a block already holds GRP x 4 waves -- one or two blocks per CU
-        bpcs = (1, 2) if v in WGRAD_GROUPS else _WGRAD_BPC
-        for bpc in bpcs:
-            blocks = int(bpc * _CUS)
-            out.append((v, max(1, -(-blocks // tiles))))
-    return sorted(set(out))
-
-
 # what a forward whose statistics come as per-tile partials pays on top of its own time: the BN
 # layer's partial-merge finalize launch (bn_stats_finalize, ~11 us per layer at batch 128,
 # profiles/r3_finalize16_steady_kernels.csv)
@@ -713,8 +561,8 @@ def _best(t: dict, kind: str, n: int):
 
 
 def plan_for(x: Tensor, w: Tensor, stride: int, pad: int) -> ConvPlan:
-    key = (tuple(x.shape), tuple(w.shape), stride, pad, x.device.index, _mode(), _V2_ON,
-           _BN_LINKS, _HALO_WIDE_ON)
+    key = (tuple(x.shape), tuple(w.shape), stride, pad, x.device.index, _mode(), cv._V2_ON,
+           _BN_LINKS, cv._HALO_WIDE_ON)
     plan = _PLANS.get(key)
     if plan is not None and (plan.tuned or torch.cuda.is_current_stream_capturing()):
         return plan
@@ -758,17 +606,16 @@ def plan_for(x: Tensor, w: Tensor, stride: int, pad: int) -> ConvPlan:
                 return us if fin else us + _FIN_PENALTY_US
 
             fns = {}
-            halo = lambda c, kc: halo_variants_for(c, k, stride, pad, x.shape[3], kc)  # noqa: E731
-            for v in (variants_for(cout) + v2_variants_for(cout) + halo(cout, cin)
-                      + split_variants_for(m_out, cout, cin * k[0] * k[1])):
+            cands = plan_candidates(x.shape[0], cin, x.shape[2], x.shape[3], cout, k, stride, pad,
+                                    _BN_LINKS)
+            for v in cands["fwd"]:
                 fns[("fwd", v)] = (lambda v=v: fwd_time(v))
             if stride == 1:
                 m_in = x.shape[0] * x.shape[2] * x.shape[3]
-                for v in (variants_for(cin) + v2_variants_for(cin) + halo(cin, cout)
-                          + split_variants_for(m_in, cin, cout * k[0] * k[1])):
+                for v in cands["bwd"]:
                     fns[("bwd", v)] = (lambda v=v: _time(
                         lambda: conv2d_bwd_data(dy, w, pad, v)))
-                if _BN_LINKS:   # the linked form: a BN input, ReLU bits and mean of x's shape
+                if cands["bwdbn"]:   # the linked form: a BN input, ReLU bits and mean of x's shape
                     bnx = torch.randn_like(x)
                     bmask = torch.randint(0, 256, (m_in * cin // 8,), device=x.device,
                                           dtype=torch.uint8)
@@ -776,7 +623,7 @@ def plan_for(x: Tensor, w: Tensor, stride: int, pad: int) -> ConvPlan:
                     from .batchnorm import acc_rep
                     bsums = torch.zeros(acc_rep() * 2 * cin, dtype=torch.float64,
                                         device=x.device)
-                    for v in variants_for(cin) + v2_variants_for(cin) + halo(cin, cout):
+                    for v in cands["bwdbn"]:
                         # timed in the epilogue form the step will run: fp64 sums into the BN's
                         # backward set where _use_link_acc picks it, else per-tile partials
                         acc = bsums if _use_link_acc(m_in, v, cin) else None
@@ -784,10 +631,10 @@ def plan_for(x: Tensor, w: Tensor, stride: int, pad: int) -> ConvPlan:
                             dy, w, pad, v, bn=(bnx, bmask, bmean), bn_acc=acc)))
             else:   # phase decomposition: per-phase heuristic (-1) or one tile for every phase
                 hw = (x.shape[2], x.shape[3])
-                for v in [-1] + variants_for(cin) + v2_variants_for(cin):
+                for v in cands["bwd"]:
                     fns[("bwd", v)] = (lambda v=v: _time(
                         lambda: conv2d_bwd_data_strided(dy, w, hw, stride, pad, v)))
-            for c in wg:
+            for c in cands["wgrad"]:
                 fns[("wgrad", c)] = (lambda c=c: _time(
                     lambda: conv2d_wgrad(x, dy, k, stride, pad, c[0], c[1])))
             ext = _ext.load()
@@ -1169,11 +1016,11 @@ def _stem_plan(z: Tensor, w16: Tensor) -> Tuple[int, Tuple[int, int]]:
         return plan
     ext = _ext.load()
     ho, wo = z.shape[2], z.shape[3]
-    fvs = [v for v in variants_for(w16.shape[0]) if TILES[v][1] == 64 and v < 12]   # c16: 4 waves
+    fvs = [v for v in variants_for(w16.shape[0]) if FWD[v].c16]
     wcs = [(3, 0), (7, 0)]
     if _mode() == "ours" or torch.cuda.is_current_stream_capturing():
         fv = pick_variant(z.shape[0] * ho * wo, w16.shape[0])
-        plan = (fv if TILES[fv][1] == 64 else 1, wcs[0])
+        plan = (fv if FWD[fv].c16 else 1, wcs[0])
         if _mode() == "ours":
             _STEM_PLANS[key] = plan
         return plan

@@ -12,15 +12,15 @@
 // reductions (at most 512 block sums per channel) add into replica 0.
 #define ARENA_ACC_REP 4
 
-// Forward-convolution variant codes (conv_kernels.hip; arena_amd/ops/conv.py TILES mirrors them and
-// tests/test_conv.py checks the copy against arena_conv_tile):
-//   v1 tile t (0 .. ARENA_CONV_V1_TILES - 1) with its K steps split over ks blocks:
-//     t + ARENA_CONV_V1_TILES * (ks - 1), below ARENA_CONV_V1_END;
-//   v2 tile i (0 .. ARENA_CONV_V2_COUNT - 1), never split: ARENA_CONV_V2_BASE + i.
-#define ARENA_CONV_V1_TILES 16
-#define ARENA_CONV_V1_END 256
-#define ARENA_CONV_V2_BASE 4096
-#define ARENA_CONV_V2_COUNT 19
+// Convolution variant codes (stable: the autotuner stores them in plans and plan files). Every
+// kernel form is ONE row of a table in conv_kernels.hip (kFwdRows / kWgradRows), from which its
+// launch is instantiated; arena_conv_variant / arena_conv_wgrad_variant return a row and
+// arena_conv_variants / arena_conv_wgrad_variants every code. arena_amd/ops/conv_variants.py holds
+// the planner's copy of the rows; tests/test_conv.py compares the two field by field.
+// Forward / backward-data codes: a row's code, and for a row that may be split
+//   code + ARENA_CONV_SPLIT_STRIDE * (ks - 1): the same tile with its K steps split over
+//   ks <= ARENA_CONV_SPLIT_STRIDE blocks.
+#define ARENA_CONV_SPLIT_STRIDE 16
 
 // ----------------------------------------------------------------------------------------------
 // Host-visible plain-C ABI structs shared with the torch binding TU (bindings.cpp).
@@ -123,6 +123,36 @@ struct ArenaBNBwd {
   // the forward's y = act((x - mean) * scale + shift): the fused stem (BN + ReLU + max pool,
   // arena_bn_pool_bwd) recomputes its ReLU mask from x with them
   const float* scale; const float* shift;
+};
+
+// One forward / backward-data convolution variant (see ARENA_CONV_SPLIT_STRIDE above).
+enum {
+  ARENA_CONV_V1 = 0,        // 16x16x32 MFMAs on 4 waves (conv_fwd_kernel / conv_wgrad_kernel)
+  ARENA_CONV_V1_W8 = 1,     // the same body on 8 waves, 256-row tiles (conv_fwd_kernel_w8)
+  ARENA_CONV_V2 = 2,        // 32x32x16 MFMAs, LDS epilogue (conv2_kernel / conv_wgrad2_kernel)
+  ARENA_CONV_V2_OCC4 = 3,   // its serial single-buffer form, four waves per SIMD
+  ARENA_CONV_V2_HALO = 4    // its 3x3 / stride 1 / pad 1 halo form (conv2_kernel_halo)
+};
+struct ArenaConvVariant {
+  int code, base;         // base: the unsplit code of the same tile (== code when ksplit == 1)
+  int bm, bn;             // output tile: pixels x channels
+  int family;             // ARENA_CONV_V1 ...
+  int nwm, nwn, nbuf;     // waves along bm / bn; stage buffers (halo: weight ring buffers)
+  int ksplit;             // split-K factor of this code
+  int max_width;          // halo: the widest image its window holds; 0: no limit
+  int even_chunks;        // two wave groups split the 64-channel chunks: C / 64 must be even
+  int wide8;              // an 8-wave halo form
+  int c16, phases;        // has a c16 (stem) form; runs strided-dgrad phases in one launch
+  int may_split;          // the codes base + ARENA_CONV_SPLIT_STRIDE * (ks - 1) exist
+};
+
+// One weight-gradient variant: a bm x bn (Cout x R*S*C) tile. family: ARENA_CONV_V1 or _V2.
+struct ArenaConvWgradVariant {
+  int code, bm, bn, family;
+  int nwm, nwn, nbuf;
+  int serial;             // single stage buffer, four waves per SIMD
+  int groups;             // wave groups per block that split its pixel steps
+  int c16;
 };
 
 // Intra-node xGMI collective (csrc/ccl/xgmi_ccl.hip): every rank's registered buffers, mapped into
@@ -256,10 +286,8 @@ hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N,
                                  const void* const* w, const int* R, const int* S,
                                  const int* pad_h, const int* pad_w, const int* Ho, const int* Wo,
                                  const int* ooh, const int* oow, int variant, hipStream_t st);
-int arena_conv_tile(int variant, int* bm, int* bn);
-long long arena_conv_fwd_ksplit_floats(long long M, int Cout, int variant, int ksplit);
-long long arena_conv_fwd_tiles(long long M, int Cout, int variant);
-int arena_conv_fwd_tile_rows(int variant);
+int arena_conv_variant(int code, ArenaConvVariant* out);
+int arena_conv_variants(int* codes, int cap);
 hipError_t arena_conv_flip_multi(int n, const void* const* src, void* const* dst, const int* cout,
                                  const int* cin, const int* rs, hipStream_t st);
 hipError_t arena_conv_phase_weights(const void* w, void* wt, int Cout, int C, int R, int S,
@@ -273,7 +301,8 @@ hipError_t arena_stem_weight(const void* w, void* w16, int Cout, int C, long lon
 hipError_t arena_stem_weight_grad(const void* dw16, void* dw, int Cout, int C, long long dco,
                                   long long dc, long long dr, long long ds, int dw_f32,
                                   hipStream_t st);
-int arena_conv_wgrad_tile(int variant, int* bm, int* bn);
+int arena_conv_wgrad_variant(int code, ArenaConvWgradVariant* out);
+int arena_conv_wgrad_variants(int* codes, int cap);
 int arena_conv_wgrad_splits(int N, int Ho, int Wo, int Cout, int Ktot, int variant,
                             int splits_hint);
 hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* dw_bf16,

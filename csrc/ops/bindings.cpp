@@ -757,36 +757,28 @@ unsigned* conv_tickets(const Tensor& like, int64_t tiles) {
   return p;
 }
 
-// conv variant code (abi.h ARENA_CONV_*): a v1 tile/pipeline variant + its split-K factor, or a
-// variant of the v2 tile kernel (conv_kernels.hip conv2_body; never split)
+// A forward variant code's row (abi.h ArenaConvVariant: its unsplit base code and split-K factor
+// among the fields) and, for a split code, the workspace and tickets of one launch
 struct ConvSplit {
-  int base = 0, ks = 1;
+  ArenaConvVariant row{};
   Tensor ws;
   unsigned* cnt = nullptr;
 };
 
 ConvSplit conv_split(const Tensor& x, int64_t variant, int64_t M, int64_t Cout, int64_t Ktot) {
   ConvSplit s;
-  TORCH_CHECK(variant >= 0, "conv: bad variant ", variant);
-  if (variant >= ARENA_CONV_V2_BASE) {
-    TORCH_CHECK(variant - ARENA_CONV_V2_BASE < ARENA_CONV_V2_COUNT, "conv: unknown v2 variant ",
-                variant);
-    s.base = (int)variant;
-  } else {
-    TORCH_CHECK(variant < ARENA_CONV_V1_END, "conv: unknown variant ", variant);
-    s.base = (int)(variant % ARENA_CONV_V1_TILES);
-    s.ks = (int)(variant / ARENA_CONV_V1_TILES) + 1;
-    int bm = 0, bn = 0;
-    arena_conv_tile(s.base, &bm, &bn);
-    TORCH_CHECK(Cout % bn == 0, "conv: variant ", variant, " needs Cout % ", bn,
-                " == 0 (Cout = ", Cout, ")");
-  }
-  if (s.ks > 1) {
-    TORCH_CHECK(s.ks <= Ktot / 64, "conv: split-K ", s.ks, " exceeds the ", Ktot / 64,
+  const ArenaConvVariant& r = s.row;
+  TORCH_CHECK(variant == (int)variant && arena_conv_variant((int)variant, &s.row),
+              "conv: unknown variant ", variant);
+  TORCH_CHECK(Cout % r.bn == 0, "conv: variant ", variant, " needs Cout % ", r.bn,
+              " == 0 (Cout = ", Cout, ")");
+  if (r.ksplit > 1) {
+    TORCH_CHECK(r.ksplit <= Ktot / 64, "conv: split-K ", r.ksplit, " exceeds the ", Ktot / 64,
                 " K steps");
-    const long long nf = arena_conv_fwd_ksplit_floats(M, (int)Cout, s.base, s.ks);
-    s.ws = torch::empty({nf}, x.options().dtype(torch::kFloat32));
-    s.cnt = conv_tickets(x, arena_conv_fwd_tiles(M, (int)Cout, s.base));
+    // ksplit fp32 copies of every output tile, one ticket per tile
+    const int64_t tiles = (M + r.bm - 1) / r.bm * (Cout / r.bn);
+    s.ws = torch::empty({tiles * r.ksplit * r.bm * r.bn}, x.options().dtype(torch::kFloat32));
+    s.cnt = conv_tickets(x, tiles);
   }
   return s;
 }
@@ -1298,7 +1290,7 @@ std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad_h, 
   } else if (bacc) {
     acc_t = *bn_acc;
   } else if (with_stats) {
-    const int rows = arena_conv_fwd_tile_rows(ks.base);
+    const int rows = ks.row.bm;
     const int64_t m_tiles = (N * Ho * Wo + rows - 1) / rows;
     part = torch::empty({m_tiles * 2 * Cout}, x.options().dtype(torch::kFloat32));
   }
@@ -1312,9 +1304,10 @@ std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad_h, 
                               bwd_bn ? bn_mean->data_ptr<float>() : nullptr, (int)N, (int)H,
                               (int)W, (int)C, (int)Cout, (int)R, (int)S, (int)stride, (int)pad_h,
                               (int)pad_w, (int)Ho, (int)Wo, mapped ? map7.data() : nullptr,
-                              c16 ? 1 : 0, ks.base,
-                              acc_t.defined() ? acc_t.data_ptr<double>() : nullptr, ks.ks,
-                              ks.ks > 1 ? ks.ws.data_ptr() : nullptr, ks.cnt, cur_stream()),
+                              c16 ? 1 : 0, ks.row.base,
+                              acc_t.defined() ? acc_t.data_ptr<double>() : nullptr, ks.row.ksplit,
+                              ks.row.ksplit > 1 ? ks.ws.data_ptr() : nullptr, ks.cnt,
+                              cur_stream()),
             "conv_fwd");
   if (acc_t.defined()) return {y, acc_t};
   if (with_stats) return {y, part};
@@ -1521,11 +1514,11 @@ Tensor conv_wgrad(Tensor x, Tensor dy, int64_t R, int64_t S, int64_t stride, int
     TORCH_CHECK(Ho == (H + 2 * pad_h - R) / stride + 1 && Wo == (W + 2 * pad_w - S) / stride + 1,
                 "conv_wgrad: dy shape does not match the convolution geometry");
   }
-  int tbm = 0, tbn = 0;
-  TORCH_CHECK(variant == (int)variant && arena_conv_wgrad_tile((int)variant, &tbm, &tbn),
+  ArenaConvWgradVariant row{};
+  TORCH_CHECK(variant == (int)variant && arena_conv_wgrad_variant((int)variant, &row),
               "conv_wgrad: unknown variant ", variant);
-  TORCH_CHECK(Cout % tbm == 0 &&
-                  (c16 ? (variant <= 7 && C == 16 && S % 4 == 0 && tbn == 64) : C % tbn == 0),
+  const int tbm = row.bm, tbn = row.bn;
+  TORCH_CHECK(Cout % tbm == 0 && (c16 ? (row.c16 && C == 16 && S % 4 == 0) : C % tbn == 0),
               "conv_wgrad: variant ", variant, " needs C % ", tbn, " == 0 and Cout % ", tbm,
               " == 0 (c16 mode: a 64-wide v1 tile, C == 16, S % 4 == 0); C = ", C, ", Cout = ",
               Cout);
@@ -1870,18 +1863,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stride"), py::arg("pad_h"), py::arg("pad_w"), py::arg("variant"),
         py::arg("splits_hint"), py::arg("out_fp32"), py::arg("scale"), py::arg("c16") = false,
         py::arg("explicit_out") = false);
-  // the kernels' tile tables (arena_amd/ops/conv.py keeps a copy that the tests check against)
-  m.def("conv_tile", [](int64_t code) {
-    int bm = 0, bn = 0;
-    TORCH_CHECK(code == (int)code && arena_conv_tile((int)code, &bm, &bn),
-                "conv_tile: unknown variant code ", code);
-    return std::make_pair(bm, bn);
+  // the kernels' variant tables (arena_amd/ops/conv_variants.py keeps the planner's copy, which
+  // the tests check against these): one row as a dict of its fields, and every code
+  static const char* const kFamily[] = {"v1", "v1_w8", "v2", "v2_occ4", "v2_halo"};
+  m.def("conv_variant", [](int64_t code) {
+    ArenaConvVariant r{};
+    TORCH_CHECK(code == (int)code && arena_conv_variant((int)code, &r),
+                "conv_variant: unknown variant code ", code);
+    py::dict d;
+    d["code"] = r.code; d["base"] = r.base; d["bm"] = r.bm; d["bn"] = r.bn;
+    d["family"] = kFamily[r.family];
+    d["nwm"] = r.nwm; d["nwn"] = r.nwn; d["nbuf"] = r.nbuf; d["ksplit"] = r.ksplit;
+    d["max_width"] = r.max_width; d["even_chunks"] = r.even_chunks != 0;
+    d["wide8"] = r.wide8 != 0; d["c16"] = r.c16 != 0; d["phases"] = r.phases != 0;
+    d["may_split"] = r.may_split != 0;
+    return d;
   });
-  m.def("conv_wgrad_tile", [](int64_t code) {
-    int bm = 0, bn = 0;
-    TORCH_CHECK(code == (int)code && arena_conv_wgrad_tile((int)code, &bm, &bn),
-                "conv_wgrad_tile: unknown variant code ", code);
-    return std::make_pair(bm, bn);
+  m.def("conv_wgrad_variant", [](int64_t code) {
+    ArenaConvWgradVariant r{};
+    TORCH_CHECK(code == (int)code && arena_conv_wgrad_variant((int)code, &r),
+                "conv_wgrad_variant: unknown variant code ", code);
+    py::dict d;
+    d["code"] = r.code; d["bm"] = r.bm; d["bn"] = r.bn; d["family"] = kFamily[r.family];
+    d["nwm"] = r.nwm; d["nwn"] = r.nwn; d["nbuf"] = r.nbuf; d["serial"] = r.serial != 0;
+    d["groups"] = r.groups; d["c16"] = r.c16 != 0;
+    return d;
+  });
+  m.def("conv_variants", [] {
+    std::vector<int> codes(arena_conv_variants(nullptr, 0));
+    arena_conv_variants(codes.data(), (int)codes.size());
+    return codes;
+  });
+  m.def("conv_wgrad_variants", [] {
+    std::vector<int> codes(arena_conv_wgrad_variants(nullptr, 0));
+    arena_conv_wgrad_variants(codes.data(), (int)codes.size());
+    return codes;
   });
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("xent_fwd", &xent_fwd);

@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <utility>
 
 #include "common.h"
 
@@ -964,7 +965,6 @@ __global__ __launch_bounds__(512) void conv_fwd_kernel_w8(ConvArgs a) {
 template <int BM, int BN>
 hipError_t launch_w8(const ConvArgs& a0, int nb, hipStream_t st) {
   ConvArgs a = a0;
-  if (a.c16) return hipErrorInvalidValue;
   a.m_tiles = (a.M + BM - 1) / BM;
   a.n_tiles = a.Cout / BN;
   const int nwg = a.m_tiles * a.n_tiles * a.ksplit;
@@ -982,14 +982,14 @@ hipError_t launch_w8(const ConvArgs& a0, int nb, hipStream_t st) {
 }
 
 template <int BM, int BN, bool C16>
-hipError_t launch_t(const ConvArgs& a0, int pipe, hipStream_t st) {
+hipError_t launch_t(const ConvArgs& a0, int nb, hipStream_t st) {
   ConvArgs a = a0;
   a.m_tiles = (a.M + BM - 1) / BM;
   a.n_tiles = a.Cout / BN;
   const int nwg = a.m_tiles * a.n_tiles * a.ksplit;
-  // stage buffers: pipe 0 (variants 0..3) two, pipe 1 (4..7) three, pipe 2 (8..11) one (serial,
-  // high occupancy); a single K step always one
-  const int nb = a.Ktot == kBK || pipe == 2 ? 1 : (pipe == 1 ? 4 : 2);
+  // nb: the row's stage buffers (2; 4: three steps in flight; 1: serial, high occupancy); a
+  // single K step always one
+  if (a.Ktot == kBK) nb = 1;
   const int epi = (a.part == nullptr && a.bn_acc == nullptr) ? 0 : (a.bnx != nullptr ? 2 : 1);
 #define ARENA_CONV_LAUNCH(E, NB) \
   hipLaunchKernelGGL((conv_fwd_kernel<BM, BN, E, NB, C16>), dim3(nwg), dim3(kThreads), 0, st, a)
@@ -1741,13 +1741,12 @@ void conv2_kernel_halo(ConvArgs a) {
 template <int BM, int BN, int HW, int NB, int NWM = 2, int NWN = 2>
 hipError_t launch2_halo(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
-  if (a.c16 || a.Cout % BN || a.R != 3 || a.S != 3 ||
-      a.stride != 1 || a.pad != 1 || a.pad_w != 1 || a.Ho != a.H || a.Wo != a.W ||
-      a.W > ((HW & 3) == 2 ? kHaloSmallW : kHaloMaxW) || a.mapped ||
-      ((HW & kHaloSplit2) && (a.C / kBK) % 2))
+  // (the row's limits -- tile width, image width, even chunk count, no c16 / split-K -- are
+  // conv_launch's checks)
+  if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.pad_w != 1 || a.Ho != a.H ||
+      a.Wo != a.W || a.mapped)
     return hipErrorInvalidValue;
   const int nthr = (HW & kHaloSplit2) ? 512 : 64 * NWM * NWN;
-  if (a.ksplit != 1) return hipErrorInvalidValue;
   if (a.bnx == nullptr && (a.part != nullptr || a.bn_acc != nullptr) && a.add != nullptr)
     return hipErrorInvalidValue;
   a.m_tiles = (a.M + BM - 1) / BM;
@@ -1768,8 +1767,6 @@ hipError_t launch2_halo(const ConvArgs& a0, hipStream_t st) {
 template <int BM, int BN, int NWM, int NWN, int NBUF, bool OCC4 = false>
 hipError_t launch2_t(const ConvArgs& a0, hipStream_t st) {
   ConvArgs a = a0;
-  if (a.c16 || a.Cout % BN) return hipErrorInvalidValue;
-  if (a.ksplit != 1) return hipErrorInvalidValue;   // split-K: the v1 tiles only
   const bool bwd_bn = a.bnx != nullptr;   // EPI 2 (the caller checked part / bnmean / no map)
   if (!bwd_bn && (a.part != nullptr || a.bn_acc != nullptr) && (a.add != nullptr || a.mapped))
     return hipErrorInvalidValue;
@@ -1807,64 +1804,139 @@ hipError_t launch2_t(const ConvArgs& a0, hipStream_t st) {
   return hipGetLastError();
 }
 
-// variant codes (abi.h): v1 tile + kV1Tiles (k - 1) with split-K k <= 16, v2 tile kV2Base + index
-constexpr int kV1Tiles = ARENA_CONV_V1_TILES;
-constexpr int kV2Base = ARENA_CONV_V2_BASE;   // above every v1 code
-constexpr int kV2Count = ARENA_CONV_V2_COUNT;
-// v2 variant table: BM x BN tile (launch2: waves NWM x NWN, stage buffers)
-constexpr int kV2Tiles[kV2Count][2] = {{256, 128}, {256, 256}, {128, 128}, {256, 64}, {128, 256},
-                                       {128, 64}, {64, 64}, {64, 128},
-                                       {128, 128}, {128, 64}, {64, 128}, {64, 64},
-                                       {128, 128}, {128, 64}, {128, 64},
-                                       {128, 128},
-                                       {256, 128}, {128, 256}, {256, 64}};
+// ------------------------------------------------------------------------------------------------
+// The forward / backward-data variant table: one row per kernel form (abi.h ArenaConvVariant). A
+// row is the form's whole description: conv_launch checks its limits and conv_launch_row
+// instantiates the launcher from it, so a row and its launch cannot disagree. A new form is one
+// row here (plus its row in arena_amd/ops/conv_variants.py).
+// ------------------------------------------------------------------------------------------------
+constexpr int kV2Base = 4096;   // the v2 tile kernel's codes: above every (split) v1 code
 
-hipError_t launch2(const ConvArgs& a, int idx, hipStream_t st) {
-  switch (idx) {
-    case 0: return launch2_t<256, 128, 4, 2, 3>(a, st);
-    case 1: return launch2_t<256, 256, 2, 4, 2>(a, st);
-    case 2: return launch2_t<128, 128, 2, 2, 2>(a, st);
-    case 3: return launch2_t<256, 64, 4, 2, 3>(a, st);
-    case 4: return launch2_t<128, 256, 2, 4, 3>(a, st);
+constexpr ArenaConvVariant v1_row(int code, int bm, int bn, int nbuf) {   // 4 waves; c16: BN = 64
+  return {code, code, bm, bn, ARENA_CONV_V1, 2, 2, nbuf, 1, 0, 0, 0, bn == 64, 0, 1};
+}
+constexpr ArenaConvVariant w8_row(int code, int bn, int nbuf) {   // 256-row tiles, 8 waves
+  return {code, code, 256, bn, ARENA_CONV_V1_W8, 4, 2, nbuf, 1, 0, 0, 0, 0, 0, 1};
+}
+// v2: never split, no c16; the tile forms run strided-dgrad phases in one launch
+constexpr ArenaConvVariant v2_row(int i, int bm, int bn, int nwm, int nwn, int nbuf) {
+  return {kV2Base + i, kV2Base + i, bm, bn, nbuf == 1 ? ARENA_CONV_V2_OCC4 : ARENA_CONV_V2,
+          nwm, nwn, nbuf, 1, 0, 0, 0, 0, 1, 0};
+}
+constexpr ArenaConvVariant halo_row(int i, int bm, int bn, int nwm, int nwn, int ring, int max_w,
+                                    int even_chunks = 0) {
+  return {kV2Base + i, kV2Base + i, bm, bn, ARENA_CONV_V2_HALO, nwm, nwn, ring, 1, max_w,
+          even_chunks, nwm * nwn == 8, 0, 0, 0};
+}
+
+constexpr ArenaConvVariant kFwdRows[] = {
+    // v1: 128x128, 128x64, 64x128, 64x64 with two stage buffers
+    v1_row(0, 128, 128, 2), v1_row(1, 128, 64, 2), v1_row(2, 64, 128, 2), v1_row(3, 64, 64, 2),
+    // + 4: a four-stage K pipeline (three glds steps in flight)
+    v1_row(4, 128, 128, 4), v1_row(5, 128, 64, 4), v1_row(6, 64, 128, 4), v1_row(7, 64, 64, 4),
+    // + 8: one stage buffer, serial K loop, high occupancy (streaming-bound 1x1 shapes)
+    v1_row(8, 128, 128, 1), v1_row(9, 128, 64, 1), v1_row(10, 64, 128, 1), v1_row(11, 64, 64, 1),
+    // 256x128 / 256x64 on 8 waves: two stage buffers, then three
+    w8_row(12, 128, 2), w8_row(13, 64, 2), w8_row(14, 128, 3), w8_row(15, 64, 3),
+    v2_row(0, 256, 128, 4, 2, 3), v2_row(1, 256, 256, 2, 4, 2), v2_row(2, 128, 128, 2, 2, 2),
+    v2_row(3, 256, 64, 4, 2, 3), v2_row(4, 128, 256, 2, 4, 3),
     // 4-wave small tiles: several blocks per CU (48 / 32 / 48 KB of LDS) for the 64-channel
     // layers, where the 8-wave 256-row tiles leave each SIMD with two waves to hide latency
-    case 5: return launch2_t<128, 64, 2, 2, 2>(a, st);
-    case 6: return launch2_t<64, 64, 2, 2, 2>(a, st);
-    case 7: return launch2_t<64, 128, 2, 2, 2>(a, st);
+    v2_row(5, 128, 64, 2, 2, 2), v2_row(6, 64, 64, 2, 2, 2), v2_row(7, 64, 128, 2, 2, 2),
     // serial high-occupancy forms of the 4-wave tiles (conv2_kernel_occ4)
-    case 8: return launch2_t<128, 128, 2, 2, 1, true>(a, st);
-    case 9: return launch2_t<128, 64, 2, 2, 1, true>(a, st);
-    case 10: return launch2_t<64, 128, 2, 2, 1, true>(a, st);
-    case 11: return launch2_t<64, 64, 2, 2, 1, true>(a, st);
+    v2_row(8, 128, 128, 2, 2, 1), v2_row(9, 128, 64, 2, 2, 1), v2_row(10, 64, 128, 2, 2, 1),
+    v2_row(11, 64, 64, 2, 2, 1),
     // 3x3 / stride 1 / pad 1 halo forms (conv2_kernel_halo); LDS per block in comments
-    case 12: return launch2_halo<128, 128, 1, 3>(a, st);   // 80 KB
-    case 13: return launch2_halo<128, 64, 1, 2>(a, st);    // 48 KB
-    case 14: return launch2_halo<128, 64, 2, 2>(a, st);    // <= 31 wide: 40 KB, 4 blocks per CU
+    halo_row(12, 128, 128, 2, 2, 3, kHaloMaxW),     // 80 KB
+    halo_row(13, 128, 64, 2, 2, 2, kHaloMaxW),      // 48 KB
+    halo_row(14, 128, 64, 2, 2, 2, kHaloSmallW),    // <= 31 wide: 40 KB, 4 blocks per CU
     // two wave groups splitting the channel chunks (512 threads, two waves per SIMD): 144 KB.
     // Measured and not kept (profiles/r6_halo_variants.jsonl): 128x128 with two groups and two
     // ring buffers, 128x64 with two groups, four- and six-deep rings, a second window buffer.
-    case 15: return launch2_halo<128, 128, 2 | kHaloSplit2, 3>(a, st);
+    halo_row(15, 128, 128, 2, 2, 3, kHaloSmallW, 1),
     // 8-wave halo forms (one block per CU, two waves per SIMD): the L2 -> LDS weight stream is
     // what bounds the 4-wave forms (16 KB per tap per 128x128 block ~ 30 B/clk per CU at full MFMA
     // rate, the measured L2 -> LDS rate; MI355X_MICROARCH.md "gather into LDS"). A 256-pixel or
     // 256-channel block halves the weight bytes per MFMA.
-    case 16: return launch2_halo<256, 128, 1, 3, 4, 2>(a, st);   // 128 KB (epilogue tile)
-    case 17: return launch2_halo<128, 256, 1, 3, 2, 4>(a, st);   // 128 KB
-    case 18: return launch2_halo<256, 64, 1, 3, 4, 2>(a, st);    // 72 KB, two blocks per CU
+    halo_row(16, 256, 128, 4, 2, 3, kHaloMaxW),     // 128 KB (epilogue tile)
+    halo_row(17, 128, 256, 2, 4, 3, kHaloMaxW),     // 128 KB
+    halo_row(18, 256, 64, 4, 2, 3, kHaloMaxW),      // 72 KB, two blocks per CU
     // (a four-buffer ring on 16 / 18, three taps in flight, measured no faster:
     // profiles/r6_halo_wide_ring4.jsonl)
-    default: return hipErrorInvalidValue;
+};
+constexpr int kFwdCount = sizeof(kFwdRows) / sizeof(kFwdRows[0]);
+constexpr bool split_codes_fit() {   // a split code must not run into another row's code
+  for (const ArenaConvVariant& r : kFwdRows)
+    if (r.may_split ? r.code >= ARENA_CONV_SPLIT_STRIDE
+                    : r.code < ARENA_CONV_SPLIT_STRIDE * ARENA_CONV_SPLIT_STRIDE)
+      return false;
+  return true;
+}
+static_assert(split_codes_fit(), "rows that may be split take the codes below the split stride");
+
+int fwd_row(int code) {   // index into kFwdRows of an unsplit code; -1: no kernel has it
+  for (int i = 0; i < kFwdCount; ++i)
+    if (kFwdRows[i].code == code) return i;
+  return -1;
+}
+
+template <int I>
+hipError_t conv_launch_row(const ConvArgs& a, hipStream_t st) {
+  constexpr ArenaConvVariant r = kFwdRows[I];
+  if constexpr (r.family == ARENA_CONV_V1) {
+    if constexpr (r.c16 != 0) {   // the stem's c16 form only exists for 64-wide tiles
+      if (a.c16) return launch_t<r.bm, r.bn, true>(a, r.nbuf, st);
+    }
+    return launch_t<r.bm, r.bn, false>(a, r.nbuf, st);
+  } else if constexpr (r.family == ARENA_CONV_V1_W8) {
+    return launch_w8<r.bm, r.bn>(a, r.nbuf, st);
+  } else if constexpr (r.family == ARENA_CONV_V2_HALO) {
+    // window size class (1: <= 63 wide, 2: <= 31) | kHaloSplit2 for the two-group form
+    constexpr int hw = (r.max_width == kHaloSmallW ? 2 : 1) | (r.even_chunks ? kHaloSplit2 : 0);
+    return launch2_halo<r.bm, r.bn, hw, r.nbuf, r.nwm, r.nwn>(a, st);
+  } else {
+    return launch2_t<r.bm, r.bn, r.nwm, r.nwn, r.nbuf, r.family == ARENA_CONV_V2_OCC4>(a, st);
   }
 }
 
-// the stem's c16 form only exists for 64-wide tiles (its Cout is 64)
-template <int BM, int BN>
-hipError_t launch(const ConvArgs& a, int pipe, hipStream_t st) {
-  if (a.c16) {
-    if constexpr (BN == 64) return launch_t<BM, BN, true>(a, pipe, st);
-    else return hipErrorInvalidValue;
+template <int... I>
+hipError_t conv_launch_index(const ConvArgs& a, int i, hipStream_t st,
+                             std::integer_sequence<int, I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((i == I && ((e = conv_launch_row<I>(a, st)), true)) || ...);
+  return e;
+}
+
+// Launches unsplit code `code` (a.ksplit carries the split factor) after the row's own limits.
+hipError_t conv_launch(const ConvArgs& a, int code, hipStream_t st) {
+  const int i = fwd_row(code);
+  if (i < 0) return hipErrorInvalidValue;
+  const ArenaConvVariant& r = kFwdRows[i];
+  if (a.Cout % r.bn || (a.c16 && !r.c16) || (a.ksplit != 1 && !r.may_split) ||
+      (a.nph > 0 && !r.phases) || (r.max_width && a.W > r.max_width) ||
+      (r.even_chunks && (a.C / kBK) % 2))
+    return hipErrorInvalidValue;
+  return conv_launch_index(a, i, st, std::make_integer_sequence<int, kFwdCount>{});
+}
+
+// The limits one convolution, or one phase of a multi-phase launch, must keep: M below 2^31,
+// every mapped output pixel inside the [Hy][Wy] image, and (descriptor staging, not c16) 31-bit
+// byte offsets and a 32-bit tap mask. Fills the operands' byte sizes.
+bool conv_limits_ok(const ConvArgs& a, int R, int S, int Ho, int Wo, int ooh, int oow, int* xbytes,
+                    int* wbytes) {
+  if (R <= 0 || S <= 0 || Ho <= 0 || Wo <= 0 || (long long)a.N * Ho * Wo >= (1LL << 31))
+    return false;
+  if (a.mapped && (ooh < 0 || oow < 0 || a.osh <= 0 || a.osw <= 0 ||
+                   (Ho - 1) * a.osh + ooh >= a.Hy || (Wo - 1) * a.osw + oow >= a.Wy))
+    return false;
+  if (!a.c16) {
+    const long long xb = (long long)a.N * a.H * a.W * a.C * 2;
+    const long long wb = (long long)a.Cout * R * S * a.C * 2;
+    if (xb >= (1LL << 31) || wb >= (1LL << 31) || R * S > 32) return false;
+    *xbytes = (int)xb;
+    *wbytes = (int)wb;
   }
-  return launch_t<BM, BN, false>(a, pipe, st);
+  return true;
 }
 
 }  // namespace
@@ -1880,10 +1952,7 @@ void arena_conv_set_dbg(int bits) { g_conv_dbg = bits; }
 
 // Returns hipErrorInvalidValue for shapes the kernel does not cover (the caller falls back to
 // MIOpen): C % 64 != 0, Cout % 64 != 0, or an unknown tile variant.
-// variant: 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64 (BM x BN output tile per block);
-// variant + 4: the same tile with a four-stage K pipeline (three glds steps in flight);
-// variant + 8: one stage buffer, serial K loop, high occupancy (streaming-bound 1x1 shapes).
-// 12 / 13: 256x128 / 256x64 on 8 waves, two stage buffers; 14 / 15: the same, three.
+// variant: an unsplit code of kFwdRows (its split factor comes as ksplit).
 // part (optional): BatchNorm partials of y, [ceil(M / BM)][2][Cout] (EPI 1 / EPI 2 epilogues).
 // General form. pad_h/pad_w: top/left padding; Ho/Wo: output size (<= 0: derived from a symmetric
 // padding); y_map {Hy, Wy, osh, osw, ooh, oow, fill_sib} (null: dense output); c16, fill_sib:
@@ -1925,7 +1994,6 @@ hipError_t arena_conv_fwd_ex(const void* x, const void* w, void* y, float* part,
   a.stride = stride; a.pad = pad_h; a.pad_w = pad_w;
   a.Ho = Ho > 0 ? Ho : (H + 2 * pad_h - R) / stride + 1;
   a.Wo = Wo > 0 ? Wo : (W + 2 * pad_w - S) / stride + 1;
-  if (a.Ho <= 0 || a.Wo <= 0) return hipErrorInvalidValue;
   a.c16 = c16;
   static const int coal = [] {
     const char* e = getenv("ARENA_CONV_COAL");
@@ -1936,28 +2004,18 @@ hipError_t arena_conv_fwd_ex(const void* x, const void* w, void* y, float* part,
     a.mapped = 1;
     a.Hy = y_map[0]; a.Wy = y_map[1]; a.osh = y_map[2]; a.osw = y_map[3];
     a.ooh = y_map[4]; a.oow = y_map[5]; a.fill_sib = y_map[6];
-    if (a.fill_sib && (a.ooh || a.oow || a.Ho != (a.Hy + a.osh - 1) / a.osh ||
-                       a.Wo != (a.Wy + a.osw - 1) / a.osw))
-      return hipErrorInvalidValue;
-    // every mapped output pixel inside the [Hy][Wy] image (the caller checked the sizes too)
-    if ((a.Ho - 1) * a.osh + a.ooh >= a.Hy || (a.Wo - 1) * a.osw + a.oow >= a.Wy || a.ooh < 0 ||
-        a.oow < 0 || a.osh <= 0 || a.osw <= 0)
-      return hipErrorInvalidValue;
   }
-  const long long M = (long long)N * a.Ho * a.Wo;
-  if (M >= (1LL << 31) || (long long)N * H * W * C >= (1LL << 40)) return hipErrorInvalidValue;
-  a.M = (int)M;
+  // (the caller checked the mapped sizes too)
+  if (!conv_limits_ok(a, R, S, a.Ho, a.Wo, a.ooh, a.oow, &a.xbytes, &a.wbytes) ||
+      (long long)N * H * W * C >= (1LL << 40))
+    return hipErrorInvalidValue;
+  if (a.fill_sib && (a.ooh || a.oow || a.Ho != (a.Hy + a.osh - 1) / a.osh ||
+                     a.Wo != (a.Wy + a.osw - 1) / a.osw))
+    return hipErrorInvalidValue;
+  a.M = N * a.Ho * a.Wo;
   a.Ktot = R * S * C;
-  const bool v2 = variant >= kV2Base && variant < kV2Base + kV2Count;
-  if (!v2 && (variant < 0 || variant >= kV1Tiles)) return hipErrorInvalidValue;
-  if (!c16) {   // descriptor staging: 31-bit byte offsets, a 32-bit tap mask
-    const long long xb = (long long)N * H * W * C * 2, wb = (long long)Cout * a.Ktot * 2;
-    if (xb >= (1LL << 31) || wb >= (1LL << 31) || R * S > 32) return hipErrorInvalidValue;
-    a.xbytes = (int)xb;
-    a.wbytes = (int)wb;
-  }
-  // split-K: every slice gets at least one K step; the caller sized kws with
-  // arena_conv_fwd_ksplit_floats and zeroed kcnt once (the kernel re-zeroes what it uses)
+  // split-K: every slice gets at least one K step; the caller sized kws with ksplit fp32 copies
+  // of every tile and zeroed kcnt once (the kernel re-zeroes what it uses)
   if (ksplit < 1 || ksplit > a.Ktot / kBK || (ksplit > 1 && (kws == nullptr || kcnt == nullptr)))
     return hipErrorInvalidValue;
   a.ksplit = ksplit;
@@ -1965,24 +2023,7 @@ hipError_t arena_conv_fwd_ex(const void* x, const void* w, void* y, float* part,
   a.kcnt = kcnt;
   a.st1p = g_conv_st1p;
   a.dbg = g_conv_dbg;
-  if (v2) {
-    if (c16) return hipErrorInvalidValue;
-    return launch2(a, variant - kV2Base, st);
-  }
-  if (variant >= 12) {   // 256-row tiles, 8 waves: 12/13 two stage buffers, 14/15 three
-    const int nb = variant >= 14 ? 3 : 2;
-    if ((variant & 1) == 0)
-      return Cout % 128 ? hipErrorInvalidValue : launch_w8<256, 128>(a, nb, st);
-    return launch_w8<256, 64>(a, nb, st);
-  }
-  const int pipe = variant >> 2;
-  switch (variant & 3) {
-    case 0: return Cout % 128 ? hipErrorInvalidValue : launch<128, 128>(a, pipe, st);
-    case 1: return launch<128, 64>(a, pipe, st);
-    case 2: return Cout % 128 ? hipErrorInvalidValue : launch<64, 128>(a, pipe, st);
-    case 3: return launch<64, 64>(a, pipe, st);
-    default: return hipErrorInvalidValue;
-  }
+  return conv_launch(a, variant, st);
 }
 
 // All phase convolutions of a strided backward-data pass in one launch of v2 tile `variant`
@@ -1995,9 +2036,8 @@ hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N,
                                  const void* const* w, const int* R, const int* S,
                                  const int* pad_h, const int* pad_w, const int* Ho, const int* Wo,
                                  const int* ooh, const int* oow, int variant, hipStream_t st) {
-  const int idx = variant - kV2Base;
-  if (idx < 0 || idx >= 12 || nph < 1 || nph > 4 || C % kBK || Cout % 64 || N <= 0)
-    return hipErrorInvalidValue;
+  // (conv_launch refuses rows without a phases form)
+  if (nph < 1 || nph > 4 || C % kBK || Cout % 64 || N <= 0) return hipErrorInvalidValue;
   ConvArgs a{};
   a.x = (const uint16_t*)x;
   a.y = (uint16_t*)y;
@@ -2006,21 +2046,14 @@ hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N,
   a.mapped = 1; a.Hy = Hy; a.Wy = Wy; a.osh = osh; a.osw = osw;
   a.coal = 1;
   a.ksplit = 1;
-  const long long xb = (long long)N * H * W * C * 2;
-  if (xb >= (1LL << 31) || osh <= 0 || osw <= 0) return hipErrorInvalidValue;
-  a.xbytes = (int)xb;
   a.nph = nph;
   for (int p = 0; p < nph; ++p) {
     ConvArgs::Phase& ph = a.ph[p];
     ph.w = (const uint16_t*)w[p];
     ph.R = R[p]; ph.S = S[p]; ph.pad = pad_h[p]; ph.pad_w = pad_w[p];
     ph.Ho = Ho[p]; ph.Wo = Wo[p]; ph.ooh = ooh[p]; ph.oow = oow[p];
-    const long long wb = (long long)Cout * R[p] * S[p] * C * 2;
-    if (wb >= (1LL << 31) || R[p] * S[p] > 32 || R[p] <= 0 || S[p] <= 0 || Ho[p] <= 0 ||
-        Wo[p] <= 0 || ooh[p] < 0 || oow[p] < 0 || (Ho[p] - 1) * osh + ooh[p] >= Hy ||
-        (Wo[p] - 1) * osw + oow[p] >= Wy || (long long)N * Ho[p] * Wo[p] >= (1LL << 31))
+    if (!conv_limits_ok(a, R[p], S[p], Ho[p], Wo[p], ooh[p], oow[p], &a.xbytes, &ph.wbytes))
       return hipErrorInvalidValue;
-    ph.wbytes = (int)wb;
   }
   // the single-convolution fields stay consistent with phase 0 (launch2_t's checks read them)
   a.w = a.ph[0].w; a.R = R[0]; a.S = S[0]; a.pad = pad_h[0]; a.pad_w = pad_w[0];
@@ -2029,46 +2062,35 @@ hipError_t arena_conv_fwd_phases(const void* x, void* y, const void* add, int N,
   a.Ktot = R[0] * S[0] * C;
   a.st1p = g_conv_st1p;
   a.dbg = g_conv_dbg;
-  return launch2(a, idx, st);
+  return conv_launch(a, variant, st);
 }
 
-// The BM x BN output tile of a variant code (abi.h; a v1 code may carry its split-K factor):
-// returns 0 for a code no kernel has.
-int arena_conv_tile(int variant, int* bm, int* bn) {
-  static const int tm[4] = {128, 128, 64, 64}, tn[4] = {128, 64, 128, 64};
-  if (variant >= kV2Base && variant < kV2Base + kV2Count) {
-    *bm = kV2Tiles[variant - kV2Base][0];
-    *bn = kV2Tiles[variant - kV2Base][1];
-    return 1;
+// The row of a variant code, with the split factor a split code carries (abi.h): returns 0 for a
+// code no kernel has.
+int arena_conv_variant(int code, ArenaConvVariant* out) {
+  int i = fwd_row(code), ks = 1;
+  if (i < 0 && code >= 0 && code < ARENA_CONV_SPLIT_STRIDE * ARENA_CONV_SPLIT_STRIDE) {
+    i = fwd_row(code % ARENA_CONV_SPLIT_STRIDE);
+    ks = code / ARENA_CONV_SPLIT_STRIDE + 1;
+    if (i >= 0 && !kFwdRows[i].may_split) i = -1;
   }
-  if (variant < 0 || variant >= ARENA_CONV_V1_END) return 0;
-  variant %= kV1Tiles;
-  if (variant >= 12) {
-    *bm = 256;
-    *bn = (variant & 1) ? 64 : 128;
-  } else {
-    *bm = tm[variant & 3];
-    *bn = tn[variant & 3];
-  }
+  if (i < 0) return 0;
+  *out = kFwdRows[i];
+  out->code = code;
+  out->ksplit = ks;
   return 1;
 }
 
-// Split-K workspace of one launch, in floats (0 when ksplit == 1), and its ticket count (tiles).
-long long arena_conv_fwd_ksplit_floats(long long M, int Cout, int variant, int ksplit) {
-  int bm, bn;   // split-K: the v1 tiles only
-  if (ksplit <= 1 || variant >= kV1Tiles || !arena_conv_tile(variant, &bm, &bn)) return 0;
-  return ((M + bm - 1) / bm) * (Cout / bn) * ksplit * bm * bn;
-}
-
-long long arena_conv_fwd_tiles(long long M, int Cout, int variant) {
-  int bm, bn;
-  if ((variant >= kV1Tiles && variant < kV2Base) || !arena_conv_tile(variant, &bm, &bn)) return 0;
-  return ((M + bm - 1) / bm) * (Cout / bn);
-}
-
-int arena_conv_fwd_tile_rows(int variant) {
-  int bm, bn;
-  return arena_conv_tile(variant, &bm, &bn) ? bm : 0;
+// Every code (the rows, then their split codes) into codes[0 .. cap); returns how many exist.
+int arena_conv_variants(int* codes, int cap) {
+  int n = 0;
+  for (int ks = 1; ks <= ARENA_CONV_SPLIT_STRIDE; ++ks)
+    for (const ArenaConvVariant& r : kFwdRows)
+      if (ks == 1 || r.may_split) {
+        if (n < cap) codes[n] = r.code + ARENA_CONV_SPLIT_STRIDE * (ks - 1);
+        ++n;
+      }
+  return n;
 }
 
 }  // extern "C"
@@ -3023,52 +3045,66 @@ __global__ __launch_bounds__(256 * GRP) void conv_wgrad2_kernel_grp(WgradArgs a)
 #endif
 }
 
-// v2 wgrad variant table (variant 8 + i): BM x BN (Cout x R*S*C), waves, stage buffers;
-// 13 / 14: the serial 128x128 form with two / four wave groups per block
-constexpr int kWg2Count = 7;
-constexpr int kWg2Tiles[kWg2Count][2] = {{128, 128}, {256, 128}, {128, 256}, {256, 256},
-                                         {128, 128}, {128, 128}, {128, 128}};
+// The weight-gradient variant table (abi.h ArenaConvWgradVariant): one row per kernel form, from
+// which wgrad_launch_row instantiates its launch. bm x bn: Cout x R*S*C.
+constexpr ArenaConvWgradVariant wg1_row(int code, int bm, int bn, int serial) {   // c16: BN = 64
+  return {code, bm, bn, ARENA_CONV_V1, 2, 2, serial ? 1 : 2, serial, 1, bn == 64};
+}
+constexpr ArenaConvWgradVariant wg2_row(int code, int bm, int bn, int nwm, int nwn, int nbuf,
+                                        int groups = 1) {
+  return {code, bm, bn, ARENA_CONV_V2, nwm, nwn, nbuf, nbuf == 1, groups, 0};
+}
+constexpr ArenaConvWgradVariant kWgradRows[] = {
+    wg1_row(0, 128, 128, 0), wg1_row(1, 128, 64, 0), wg1_row(2, 64, 128, 0), wg1_row(3, 64, 64, 0),
+    // + 4: the serial single-buffer high-occupancy form of the same tile
+    wg1_row(4, 128, 128, 1), wg1_row(5, 128, 64, 1), wg1_row(6, 64, 128, 1), wg1_row(7, 64, 64, 1),
+    // the v2 kernel: 128/256-wide tiles, two steps in flight
+    wg2_row(8, 128, 128, 2, 2, 2), wg2_row(9, 256, 128, 4, 2, 2), wg2_row(10, 128, 256, 2, 4, 2),
+    wg2_row(11, 256, 256, 2, 4, 2),
+    wg2_row(12, 128, 128, 2, 2, 1),   // serial single-buffer, four waves per SIMD
+    // 12 with two / four wave groups per block splitting its pixel steps
+    wg2_row(13, 128, 128, 2, 2, 1, 2), wg2_row(14, 128, 128, 2, 2, 1, 4),
+};
+constexpr int kWgradCount = sizeof(kWgradRows) / sizeof(kWgradRows[0]);
 
-template <int BM, int BN, int NWM, int NWN, int NBUF, bool OCC4 = false, int GRP = 1>
-hipError_t launch_wgrad2(WgradArgs a, int splits_hint, hipStream_t st) {
-  a.m_tiles = a.Cout / BM;
-  a.n_tiles = a.Ktot / BN;
-  const int tiles = a.m_tiles * a.n_tiles;
-  const int total = (a.M + 63) / 64;
-  int splits = splits_hint > 0 ? splits_hint : std::max(1, (1024 + tiles / 2) / tiles);
-  splits = std::min(splits, total);
-  a.sps = (total + splits - 1) / splits;
-  a.splits = (total + a.sps - 1) / a.sps;
-  if constexpr (GRP > 1) {
-    hipLaunchKernelGGL((conv_wgrad2_kernel_grp<BM, BN, GRP>), dim3(tiles * a.splits),
-                       dim3(256 * GRP), 0, st, a);
-  } else if constexpr (OCC4) {
-    hipLaunchKernelGGL((conv_wgrad2_kernel_occ4<BM, BN>), dim3(tiles * a.splits), dim3(256), 0,
-                       st, a);
-  } else {
-    hipLaunchKernelGGL((conv_wgrad2_kernel<BM, BN, NWM, NWN, NBUF>), dim3(tiles * a.splits),
-                       dim3(64 * NWM * NWN), 0, st, a);
-  }
-  return hipGetLastError();
+int wgrad_row(int code) {   // index into kWgradRows; -1: no kernel has the code
+  for (int i = 0; i < kWgradCount; ++i)
+    if (kWgradRows[i].code == code) return i;
+  return -1;
 }
 
-template <int BM, int BN>
-hipError_t launch_wgrad(WgradArgs a, int splits_hint, bool serial, hipStream_t st) {
-  a.m_tiles = a.Cout / BM;
-  a.n_tiles = a.Ktot / BN;
-  const int tiles = a.m_tiles * a.n_tiles;
-  const int total = (a.M + 63) / 64;
+// The split slabs a launch over `tiles` tiles of M output pixels uses (hint <= 0: about 1024
+// blocks), and the 64-pixel steps each takes. The workspace is sized with the same number.
+int wgrad_splits(long long M, int tiles, int splits_hint, int* sps) {
+  const int total = (int)((M + 63) / 64);
   int splits = splits_hint > 0 ? splits_hint : std::max(1, (1024 + tiles / 2) / tiles);
   splits = std::min(splits, total);
-  a.sps = (total + splits - 1) / splits;
-  a.splits = (total + a.sps - 1) / a.sps;
-  if (serial)
-    hipLaunchKernelGGL((conv_wgrad_kernel_occ4<BM, BN>), dim3(tiles * a.splits), dim3(kThreads), 0,
-                       st, a);
+  *sps = (total + splits - 1) / splits;
+  return (total + *sps - 1) / *sps;
+}
+
+template <int I>   // a: tiles and splits filled in (arena_conv_wgrad_ex)
+void wgrad_launch_row(const WgradArgs& a, hipStream_t st) {
+  constexpr ArenaConvWgradVariant r = kWgradRows[I];
+  const dim3 grid(a.m_tiles * a.n_tiles * a.splits);
+  if constexpr (r.family == ARENA_CONV_V1 && r.serial != 0)
+    hipLaunchKernelGGL((conv_wgrad_kernel_occ4<r.bm, r.bn>), grid, dim3(kThreads), 0, st, a);
+  else if constexpr (r.family == ARENA_CONV_V1)
+    hipLaunchKernelGGL((conv_wgrad_kernel<r.bm, r.bn>), grid, dim3(kThreads), 0, st, a);
+  else if constexpr (r.groups > 1)
+    hipLaunchKernelGGL((conv_wgrad2_kernel_grp<r.bm, r.bn, r.groups>), grid, dim3(256 * r.groups),
+                       0, st, a);
+  else if constexpr (r.serial != 0)
+    hipLaunchKernelGGL((conv_wgrad2_kernel_occ4<r.bm, r.bn>), grid, dim3(256), 0, st, a);
   else
-    hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN>), dim3(tiles * a.splits), dim3(kThreads), 0, st,
-                       a);
-  return hipGetLastError();
+    hipLaunchKernelGGL((conv_wgrad2_kernel<r.bm, r.bn, r.nwm, r.nwn, r.nbuf>), grid,
+                       dim3(64 * r.nwm * r.nwn), 0, st, a);
+}
+
+template <int... I>
+void wgrad_launch_index(const WgradArgs& a, int i, hipStream_t st,
+                        std::integer_sequence<int, I...>) {
+  (void)((i == I && (wgrad_launch_row<I>(a, st), true)) || ...);
 }
 
 }  // namespace
@@ -3076,47 +3112,39 @@ hipError_t launch_wgrad(WgradArgs a, int splits_hint, bool serial, hipStream_t s
 
 extern "C" {
 
+int arena_conv_wgrad_variant(int code, ArenaConvWgradVariant* out) {
+  const int i = wgrad_row(code);
+  if (i >= 0) *out = kWgradRows[i];
+  return i >= 0;
+}
 
-// The Cout x R*S*C tile of a weight-gradient variant (0..3, + 4 serial: v1; 8..: the v2 kernel's
-// kWg2Tiles): returns 0 for a code no kernel has.
-int arena_conv_wgrad_tile(int variant, int* bm, int* bn) {
-  static const int tm[4] = {128, 128, 64, 64}, tn[4] = {128, 64, 128, 64};
-  if (variant < 0 || variant >= 8 + kWg2Count) return 0;
-  *bm = variant >= 8 ? kWg2Tiles[variant - 8][0] : tm[variant & 3];
-  *bn = variant >= 8 ? kWg2Tiles[variant - 8][1] : tn[variant & 3];
-  return 1;
+int arena_conv_wgrad_variants(int* codes, int cap) {
+  for (int i = 0; i < kWgradCount && i < cap; ++i) codes[i] = kWgradRows[i].code;
+  return kWgradCount;
 }
 
 // Number of split slabs the wgrad launch will use (the caller sizes the workspace with it).
 int arena_conv_wgrad_splits(int N, int Ho, int Wo, int Cout, int Ktot, int variant,
                             int splits_hint) {
-  int tbm, tbn;
-  if (!arena_conv_wgrad_tile(variant, &tbm, &tbn)) return -1;
-  const int tiles = (Cout / tbm) * (Ktot / tbn);
-  const long long M = (long long)N * Ho * Wo;
-  const int total = (int)((M + 63) / 64);
-  int splits = splits_hint > 0 ? splits_hint : std::max(1, (1024 + tiles / 2) / tiles);
-  splits = std::min(splits, total);
-  const int sps = (total + splits - 1) / splits;
-  return (total + sps - 1) / sps;
+  const int i = wgrad_row(variant);
+  if (i < 0) return -1;
+  int sps;
+  return wgrad_splits((long long)N * Ho * Wo, (Cout / kWgradRows[i].bm) * (Ktot / kWgradRows[i].bn),
+                      splits_hint, &sps);
 }
 
-// variant: 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64 (Cout x R*S*C tile); + 4: serial
-// single-buffer high-occupancy form of the same tile. Needs C % BN == 0
-// (a tile never straddles two filter taps) and Cout % BM == 0; c16 mode: C == 16, S % 4 == 0 and
-// BN == 64 (variants 1 and 3). Ho/Wo <= 0: derived from a symmetric padding.
+// variant: a code of kWgradRows. Needs C % bn == 0 (a tile never straddles two filter taps) and
+// Cout % bm == 0; c16 mode: C == 16, S % 4 == 0 and a row with a c16 form (v1, bn == 64).
+// Ho/Wo <= 0: derived from a symmetric padding.
 hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* dw_bf16,
                                float* dw_f32, int N, int H, int W, int C, int Cout, int R, int S,
                                int stride, int pad_h, int pad_w, int Ho, int Wo, int c16,
                                int variant, int splits_hint, float scale, hipStream_t st) {
-  int tbm, tbn;
-  if (!arena_conv_wgrad_tile(variant, &tbm, &tbn)) return hipErrorInvalidValue;
-  const bool v2 = variant >= 8;
-  const int tv = variant & 3;
-  const bool serial = !v2 && variant >= 4;
-  if (v2 && c16) return hipErrorInvalidValue;
-  if (c16 ? (C != 16 || S % 4 || tbn != 64) : (C % tbn != 0)) return hipErrorInvalidValue;
-  if (Cout % tbm || N <= 0 || stride <= 0) return hipErrorInvalidValue;
+  const int row = wgrad_row(variant);
+  if (row < 0) return hipErrorInvalidValue;
+  const ArenaConvWgradVariant& r = kWgradRows[row];
+  if (c16 ? (C != 16 || S % 4 || !r.c16) : (C % r.bn != 0)) return hipErrorInvalidValue;
+  if (Cout % r.bm || N <= 0 || stride <= 0) return hipErrorInvalidValue;
   WgradArgs a{};
   a.x = (const uint16_t*)x;
   a.dy = (const uint16_t*)dy;
@@ -3143,25 +3171,13 @@ hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* d
   a.Ktot = R * S * C;
   a.div_hw = make_fastdiv((uint32_t)(a.Ho * a.Wo));
   a.div_w = make_fastdiv((uint32_t)a.Wo);
-  hipError_t e;
-  if (v2) {
-    switch (variant - 8) {
-      case 0: e = launch_wgrad2<128, 128, 2, 2, 2>(a, splits_hint, st); break;
-      case 1: e = launch_wgrad2<256, 128, 4, 2, 2>(a, splits_hint, st); break;
-      case 2: e = launch_wgrad2<128, 256, 2, 4, 2>(a, splits_hint, st); break;
-      case 3: e = launch_wgrad2<256, 256, 2, 4, 2>(a, splits_hint, st); break;
-      case 5: e = launch_wgrad2<128, 128, 2, 2, 1, false, 2>(a, splits_hint, st); break;
-      case 6: e = launch_wgrad2<128, 128, 2, 2, 1, false, 4>(a, splits_hint, st); break;
-      default: e = launch_wgrad2<128, 128, 2, 2, 1, true>(a, splits_hint, st); break;
-    }
-  } else switch (tv) {
-    case 0: e = launch_wgrad<128, 128>(a, splits_hint, serial, st); break;
-    case 1: e = launch_wgrad<128, 64>(a, splits_hint, serial, st); break;
-    case 2: e = launch_wgrad<64, 128>(a, splits_hint, serial, st); break;
-    default: e = launch_wgrad<64, 64>(a, splits_hint, serial, st); break;
-  }
+  a.m_tiles = Cout / r.bm;
+  a.n_tiles = a.Ktot / r.bn;
+  a.splits = wgrad_splits(M, a.m_tiles * a.n_tiles, splits_hint, &a.sps);
+  wgrad_launch_index(a, row, st, std::make_integer_sequence<int, kWgradCount>{});
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int splits = arena_conv_wgrad_splits(N, a.Ho, a.Wo, Cout, a.Ktot, variant, splits_hint);
+  const int splits = a.splits;
   const long long n4 = (long long)Cout * a.Ktot / 4;  // Cout % 64 == 0
   // the 8 x 32 shape while 32-column blocks would not give every CU a block
   if (n4 < 32LL * 256 && splits >= 64)

@@ -5,11 +5,16 @@ variant on shapes with padding, stride 2, 1x1/3x3 taps and output-pixel counts t
 multiple of the tile (tail rows); the autotuned ``Conv2dNHWC`` module under bf16 autocast; a
 ResNet training step with the kernels equal to the MIOpen one. CPU: the module is nn.Conv2d.
 """
+import json
+import pathlib
+
 import pytest
 import torch
 import torch.nn.functional as F
 
-from arena_amd.ops import conv
+from arena_amd.ops import conv, conv_variants
+
+GOLDEN = pathlib.Path(__file__).parent / "golden"
 
 SHAPES = [  # n, cin, h, w, cout, k, stride
     (2, 64, 9, 11, 64, 3, 1),
@@ -340,24 +345,110 @@ def test_conv_kernel_rejects_bad_shapes():
     assert conv.kernel_ok(x3, w3, 1, 2) and not conv.kernel_ok(x3, w3, 1, 3)
 
 
+def test_variant_tables_match_the_fixture():
+    """tests/golden/conv_variants.json is the full row of every code, transcribed from the
+    kernels' launch switches as they stood before the tables became rows: the Python tables
+    (and through test_python_tile_tables_match_the_kernels the kernels' rows) equal it."""
+    want = json.loads((GOLDEN / "conv_variants.json").read_text())
+    assert [r._asdict() for r in sorted(conv_variants.FWD_ROWS)] == want["fwd"]
+    assert [r._asdict() for r in sorted(conv_variants.WGRAD_ROWS)] == want["wgrad"]
+    # the derived {code: tile} views: the rows' tiles, and each offered split code its base's
+    tiles = {r["code"]: (r["bm"], r["bn"]) for r in want["fwd"]}
+    assert {c: t for c, t in conv.TILES.items() if conv.split_of(c) == 1} == tiles
+    assert all(t == tiles[conv.fwd_variant(c).base] for c, t in conv.TILES.items())
+    assert conv.WGRAD_TILES == {r["code"]: (r["bm"], r["bn"]) for r in want["wgrad"]}
+
+
+def test_plan_candidates_match_the_recorded_lists():
+    """tests/golden/conv_candidates.json: the candidate lists, in timing order (which decides
+    ties), that the enumerators gave for every ResNet-50 convolution at batch 128 and this file's
+    SHAPES / V2_SHAPES before the variant tables became rows, with each A/B switch off in turn."""
+    recs = json.loads((GOLDEN / "conv_candidates.json").read_text())
+    assert len(recs) >= 4 * 30
+    try:
+        for rec in recs:
+            n, cin, h, w, cout, k, st, pad = rec["shape"]
+            conv.set_v2(rec["v2"])
+            conv.set_halo_wide(rec["halo_wide"])
+            got = conv.plan_candidates(n, cin, h, w, cout, (k, k), st, pad, rec["bn_links"])
+            got["wgrad"] = [list(c) for c in got["wgrad"]]
+            assert got == rec["candidates"], rec["shape"]
+    finally:
+        conv.set_v2(True)
+        conv.set_halo_wide(True)
+
+
 @pytest.mark.gpu
 def test_python_tile_tables_match_the_kernels():
-    """conv.TILES / conv.WGRAD_TILES are copies (the planner and the CPU tests use them without
-    the extension) of the tables in conv_kernels.hip: every code, split-K codes included, maps to
-    the same tile, and codes next to the tables' ends are unknown to both. Launches nothing."""
+    """The tables of conv_variants.py are copies (the planner and the CPU tests use them without
+    the extension) of the rows in conv_kernels.hip: both sides know the same codes and every
+    field of every row is equal; the split-K codes the planner does not offer (factors outside
+    KSPLITS) agree through split_of and the base tile; codes next to the tables' ends are unknown
+    to both. Launches nothing."""
     from arena_amd.ops import _ext
     ext = _ext.load()
-    for code, tile in conv.TILES.items():
-        assert ext.conv_tile(code) == tile, code
-    for code, tile in conv.WGRAD_TILES.items():
-        assert ext.conv_wgrad_tile(code) == tile, code
+    offered = (1,) + conv.KSPLITS
+    kcodes = ext.conv_variants()
+    assert len(kcodes) == len(set(kcodes))
+    assert {c for c in kcodes if ext.conv_variant(c)["ksplit"] in offered} == set(conv.TILES)
+    for code in kcodes:
+        row = ext.conv_variant(code)
+        assert row == conv.fwd_variant(code)._asdict(), code
+        assert conv.split_of(code) == row["ksplit"]
+        assert conv.TILES[row["base"]] == (row["bm"], row["bn"]), code
+        assert (code in conv.TILES) == (row["ksplit"] in offered), code
+    wcodes = ext.conv_wgrad_variants()
+    assert len(wcodes) == len(set(wcodes)) and set(wcodes) == set(conv.WGRAD_TILES)
+    for code in wcodes:
+        assert ext.conv_wgrad_variant(code) == conv.WGRAD[code]._asdict(), code
     for bad in (conv.V2 + len(conv.V2_TILES), -1, 256):
         assert bad not in conv.TILES
+        with pytest.raises(KeyError):
+            conv.fwd_variant(bad)
         with pytest.raises(RuntimeError, match="unknown variant"):
-            ext.conv_tile(bad)
+            ext.conv_variant(bad)
     assert 15 not in conv.WGRAD_TILES
     with pytest.raises(RuntimeError, match="unknown variant"):
-        ext.conv_wgrad_tile(15)
+        ext.conv_wgrad_variant(15)
+
+
+@pytest.mark.gpu
+def test_every_kernel_variant_runs_once():
+    """Every code of the kernels' tables, launched once at the smallest shape all of them take
+    (<= 31 wide, four 64-channel chunks, 36 K steps, 256 channels on both sides): forward and
+    backward-data of every forward code the enumerators offer (unsplit, split-K at KSPLITS, v2
+    tiles, halo forms), the weight gradient of every wgrad code at splits 1 and 0, against fp32
+    torch. The codes come from the Python enumerators and must cover the kernels' enumeration:
+    an enumerator that drops a form fails here instead of losing coverage."""
+    from arena_amd.ops import _ext
+    ext = _ext.load()
+    n, c, h, w, k, pad = 2, 256, 6, 10, 3, 1
+    x, wt = _data(n, c, h, w, c, k, "cuda", seed=7)
+    ref = F.conv2d(x.float(), wt.float(), padding=pad)
+    dy = torch.randn(ref.shape, device="cuda").to(torch.bfloat16).contiguous(
+        memory_format=torch.channels_last)
+    dx_ref, dw_ref, _ = torch.ops.aten.convolution_backward(
+        dy.float(), x.float(), wt.float(), None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
+        [True, True, False])
+    wf = conv.flip_weight(wt)
+    unsplit = conv.variants_for(c)
+    codes = (unsplit + [conv.kvariant(v, ks) for v in unsplit for ks in conv.KSPLITS]
+             + conv.v2_variants_for(c) + conv.halo_variants_for(c, (k, k), 1, pad, w, c))
+    for v in codes:
+        y = conv.conv2d_fwd(x, wt, 1, pad, v)
+        assert _rel(y, ref) < 1e-2, (v, _rel(y, ref))
+        dx = conv.conv2d_bwd_data(dy, wt, pad, v, wflip=wf)
+        assert _rel(dx, dx_ref) < 1e-2, (v, _rel(dx, dx_ref))
+    # the kernels' enumeration, less the split factors the planner never offers
+    offered = (1,) + conv.KSPLITS
+    listed = {v for v in ext.conv_variants() if ext.conv_variant(v)["ksplit"] in offered}
+    assert len(codes) == len(set(codes)) and set(codes) == listed
+    wcodes = conv.wgrad_variants_for(c, c)
+    for v in wcodes:
+        for sp in (1, 0):
+            dw = conv.conv2d_wgrad(x, dy, (k, k), 1, pad, v, sp, out_dtype=torch.float32)
+            assert _rel(dw, dw_ref) < 5e-3, (v, sp, _rel(dw, dw_ref))
+    assert len(wcodes) == len(set(wcodes)) and set(wcodes) == set(ext.conv_wgrad_variants())
 
 
 @pytest.mark.gpu
