@@ -10,7 +10,10 @@ This is the same workload, built for MI355X:
 * momentum SGD with weight decay, as in tf_cnn_benchmarks;
 * one process per GPU: ``hvd.DistributedOptimizer`` buckets (RCCL or the xGMI kernel on a comm
   stream) overlap the gradient allreduce with backward;
-* output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``.
+* output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``;
+* by default one static random batch; with ``--data_dir`` / ``--synth_images`` a uint8 dataset
+  resident in GPU memory, fed by one kernel at the head of every (captured) step
+  (``arena_amd.ops.data.DeviceImageLoader``), with epochs and an ``--eval`` pass over ``val``.
 
     arena submit mpijob --name r50 --workers 8 --gpus 1 \\
         "python -m arena_amd.examples.cnn_bench --model resnet50 --batch_size 128"
@@ -79,10 +82,75 @@ def parse(argv=None):
                     help="forward-only run (model.eval(), no optimizer): images/sec lines, then "
                          "tf_cnn_benchmarks' 'Accuracy @ 1 = ... Accuracy @ 5 = ...' line")
     ap.add_argument("--json", action="store_true", help="print one JSON summary line at the end")
+    ap.add_argument("--data_dir", default=None,
+                    help="train on the image shards of this directory (arena_amd.data.images; the "
+                         "mount point of 'arena submit --data'), resident in GPU memory; "
+                         "num_classes comes from its meta. Default: one static random batch")
+    ap.add_argument("--synth_images", type=int, default=0, metavar="N",
+                    help="train on a resident synthetic dataset of N learnable images (no files); "
+                         "--eval reads a second draw of N // 10 images")
+    ap.add_argument("--stored_size", type=int, default=0,
+                    help="stored size S of the synthetic images (default image_size * 8 // 7); "
+                         "each step crops image_size x image_size out of it")
+    ap.add_argument("--num_epochs", type=int, default=0,
+                    help="with a dataset: train this many epochs (overrides --num_batches)")
+    ap.add_argument("--data_seed", type=int, default=0,
+                    help="seed of the shuffle, the crops / flips and the synthetic images")
     args = ap.parse_args(argv)
     if not 0.0 <= args.label_smoothing <= 1.0:
         ap.error("--label_smoothing must lie in [0, 1]")
+    if args.data_dir and args.synth_images:
+        ap.error("--data_dir and --synth_images exclude each other")
+    if (args.num_epochs or args.stored_size) and not has_data(args):
+        ap.error("--num_epochs / --stored_size need --data_dir or --synth_images")
     return args
+
+
+def has_data(args) -> bool:
+    return bool(getattr(args, "data_dir", None)) or getattr(args, "synth_images", 0) > 0
+
+
+def synth_val_count(n: int) -> int:
+    """Validation images that go with ``--synth_images n``."""
+    return max(1, n // 10)
+
+
+def open_data(args, dev, world, rank, split):
+    """This rank's resident shard of the run's dataset: ``(images, labels, meta, name)``; sets
+    ``args.num_classes`` from the data."""
+    from ..data import images as imgdata
+    if args.data_dir:
+        im, lb, meta = imgdata.load_images(args.data_dir, split, dev, rank, world)
+        name = args.data_dir
+    else:
+        size = args.stored_size or args.image_size * 8 // 7
+        n = args.synth_images if split == "train" else synth_val_count(args.synth_images)
+        if n < world:
+            raise SystemExit(f"--synth_images: {n} {split} images for {world} ranks")
+        imgdata.check_fits(n * size * size * 3, dev, 16.0)
+        im, lb = imgdata.synthetic_images(n, size, args.num_classes, args.data_seed,
+                                          draw=0 if split == "train" else 1, device=dev)
+        if world > 1:
+            im, lb = im[rank::world].contiguous(), lb[rank::world].contiguous()
+        meta = {"num_classes": args.num_classes, "mean": list(imgdata.IMAGENET_MEAN),
+                "std": list(imgdata.IMAGENET_STD), "size": size, "n": n}
+        name = "synthetic-images"
+    args.num_classes = meta["num_classes"]
+    if args.image_size % 2 or args.image_size > meta["size"]:
+        raise SystemExit(f"--image_size {args.image_size} must be even and at most the stored "
+                         f"size {meta['size']}")
+    return im, lb, meta, name
+
+
+def make_loader(args, dev, rank, model, data, train):
+    """The device loader over ``open_data``'s shard, in the layout the model's stem takes."""
+    from ..ops.data import DeviceImageLoader
+    im, lb, meta, _ = data
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    s2d = args.data_format == "NHWC" and model.takes_s2d(dev, dtype)
+    return DeviceImageLoader(im, lb, args.batch_size, args.image_size, train=train,
+                             seed=args.data_seed, stream=rank, mean=meta["mean"], std=meta["std"],
+                             layout="s2d" if s2d else "nhwc", dtype=dtype)
 
 
 def build_model(args, dev):
@@ -157,7 +225,8 @@ def build(args, dev, world):
     if world > 1 and not master:
         opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
                                        bucket_mb=args.bucket_mb, comm=args.comm)
-    x, y = synthetic_batch(args, dev)
+    # with a dataset (--data_dir / --synth_images) the batch comes from the device loader
+    x, y = (None, None) if has_data(args) else synthetic_batch(args, dev)
     return model, opt, x, y
 
 
@@ -181,12 +250,21 @@ def comms_of(opt) -> list:
     return [getattr(opt, "xgmi", None)]
 
 
-def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None):
+def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None, loader=None,
+               loss_sum=None):
     """One training step. ``head``: keyword arguments for ``ops.pool.cross_entropy``
-    (``label_smoothing``, ``stats``, ``ignore_index``); None is the plain mean loss."""
+    (``label_smoothing``, ``stats``, ``ignore_index``); None is the plain mean loss.
+    ``loader``: a ``DeviceImageLoader`` whose ``next()`` opens the step (x and y are then its
+    static buffers), so a captured step holds the input pipeline and every replay advances.
+    ``loss_sum``: a device scalar the step adds its loss to (an epoch's mean without a host read
+    or a launch between replays)."""
+    s2d = False
+    if loader is not None:
+        x, y = loader.next()
+        s2d = loader.layout == "s2d"
     with torch.autocast(device_type=x.device.type, dtype=amp_dtype, enabled=amp_dtype is not None,
                         cache_enabled=False):
-        logits = model(x)
+        logits = model(x, s2d=True) if s2d else model(x)
     # (outside autocast: the fused loss takes the bf16 logits as they are and sums in fp32, as
     # autocast's fp32 cross_entropy does after its upcast copy)
     if head is not None:
@@ -204,17 +282,20 @@ def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None):
         from ..ops import conv
         conv.sync_wgrad()   # weight gradients computed on the side stream (if enabled)
     opt.step()
+    if loss_sum is not None:
+        loss_sum.add_(loss.detach().float())
     return loss.detach()
 
 
-def capture_step(model, opt, x, y, amp_dtype, *, head=None):
+def capture_step(model, opt, x, y, amp_dtype, *, head=None, loader=None, loss_sum=None):
     """The whole step as one hipGraph: ~800 kernels per ResNet-50 step replay without host
     launches or inter-kernel gaps. Gradients are None at capture, so the captured backward writes
     (not accumulates) them, and every replay reuses the same memory (static x, y)."""
     opt.zero_grad(set_to_none=True)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, capture_error_mode="thread_local"):
-        loss = train_step(model, opt, x, y, amp_dtype, zero_grad=False, head=head)
+        loss = train_step(model, opt, x, y, amp_dtype, zero_grad=False, head=head, loader=loader,
+                          loss_sum=loss_sum)
     return g, loss
 
 
@@ -238,7 +319,25 @@ def main(argv=None) -> int:
         conv.set_async_wgrad(args.async_wgrad == "on")
     if args.eval:
         return evaluate(args, dev, world, rank, amp)
+    data = loader = None
+    if has_data(args):
+        data = open_data(args, dev, world, rank, "train")    # sets args.num_classes
     model, opt, x, y = build(args, dev, world)
+    data_name = "synthetic"
+    spe = 0                       # steps per epoch, the same on every rank
+    ep_loss, ep_steps = None, 0   # the running epoch's loss sum (device) and step count (host)
+    if data is not None:
+        loader = make_loader(args, dev, rank, model, data, train=True)
+        x, y = loader.out, loader.labels_out
+        ep_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        meta = data[2]
+        spe = (meta["n"] // world) // args.batch_size
+        if spe < 1:
+            raise SystemExit(f"{meta['n']} images over {world} ranks do not fill one batch of "
+                             f"{args.batch_size}")
+        if args.num_epochs:
+            args.num_batches = args.num_epochs * spe
+        data_name = f"{data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size})"
     head = stats = None
     if args.label_smoothing != 0.0 or args.print_training_accuracy:
         # [kept, top-1, top-5, invalid labels], added to by the loss kernels on the device (so a
@@ -253,11 +352,11 @@ def main(argv=None) -> int:
     if rank == 0:
         print(f"Model: {args.model}  Batch size: {args.batch_size} per device, "
               f"{args.batch_size * world} global  Devices: {world} x {dev.type}  "
-              f"Data: synthetic  dtype: {args.dtype}  graph: {args.graph}  comm: "
+              f"Data: {data_name}  dtype: {args.dtype}  graph: {args.graph}  comm: "
               f"{comm_name(opt)}", flush=True)
     for i in range(args.num_warmup_batches):
         t = time.perf_counter()
-        train_step(model, opt, x, y, amp, head=head)
+        train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss)
         sync()
         if rank == 0:   # the first steps include MIOpen's solver search: show progress
             print(f"warmup {i + 1}/{args.num_warmup_batches}: {time.perf_counter() - t:.2f} s",
@@ -270,7 +369,8 @@ def main(argv=None) -> int:
         # exactly where eager mode issues them; all ranks replay the same collective sequence.
         ok = True
         try:
-            graph, g_loss = capture_step(model, opt, x, y, amp, head=head)
+            graph, g_loss = capture_step(model, opt, x, y, amp, head=head, loader=loader,
+                                         loss_sum=ep_loss)
         except RuntimeError as e:  # capture refused by a library call: run eagerly
             graph, ok = None, False
             print(f"[rank {rank}] hipGraph capture failed, running eagerly: {e}", flush=True)
@@ -293,14 +393,24 @@ def main(argv=None) -> int:
         check = ReplicaCheck(args.verify_every, lambda: list(model.parameters()),
                              comms=comms_of(opt))
     seen0 = seen = stats.tolist() if stats is not None else None   # warm-up's counts excluded
+    if loader is not None:
+        # epoch 1 starts here, after warm-up's batches. The host knows the step count, so the
+        # reshuffle between replays needs no device read; the epoch's loss sum stays on the device
+        loader.new_epoch()
+        ep_loss.zero_()
     t0 = t_last = time.perf_counter()
     loss = None
     for i in range(1, args.num_batches + 1):
+        if loader is not None and i > 1 and (i - 1) % spe == 0:
+            loader.new_epoch()
+            ep_loss.zero_()
+            ep_steps = 0
         if graph is not None:
             graph.replay()
             loss = g_loss
         else:
-            loss = train_step(model, opt, x, y, amp, head=head)
+            loss = train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss)
+        ep_steps += 1
         heartbeat.beat(i)
         if check is not None:
             check.maybe(i)
@@ -345,6 +455,12 @@ def main(argv=None) -> int:
                    "final_loss": round(float(loss), 4)}
             if counts is not None:
                 res.update(accuracy_fields(counts))
+            if loader is not None:
+                res.update({"data": data[3], "images": data[2]["n"], "layout": loader.layout,
+                            "steps_per_epoch": spe, "epochs": loader.epoch,
+                            "last_epoch_loss": round(float(ep_loss) / max(ep_steps, 1), 4)})
+                if counts is not None:
+                    res["kept"] = counts[0]
             print(json.dumps(res), flush=True)
     if rank == 0 and os.environ.get("ARENA_CONV_LOG"):
         from ..ops import conv
@@ -386,6 +502,8 @@ def evaluate(args, dev, world, rank, amp) -> int:
     tf_cnn_benchmarks' accuracy line, counted over all ranks."""
     from ..ops.pool import cross_entropy
     from ..parallel import hvd
+    if has_data(args):
+        return evaluate_data(args, dev, world, rank, amp)
     model = build_model(args, dev).eval()
     x, y = synthetic_batch(args, dev)
     stats = torch.zeros(4, dtype=torch.int64, device=dev)
@@ -445,6 +563,80 @@ def evaluate(args, dev, world, rank, amp) -> int:
                    "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
                    "batch_per_device": args.batch_size, "devices": world, "dtype": args.dtype,
                    "exec": "eval", "final_loss": round(float(loss), 4)}
+            res.update(accuracy_fields(counts))
+            print(json.dumps(res), flush=True)
+    hvd.shutdown()
+    return invalid_labels_error(counts, rank)
+
+
+def evaluate_data(args, dev, world, rank, amp) -> int:
+    """``--eval`` with a dataset: one pass over this rank's rows of the ``val`` split in order
+    (centre crop, no flip), ``ceil(rows / batch)`` batches. The loader pads the last batch with
+    label -100, which the loss ignores, so the example count is the number of validation images
+    exactly."""
+    from ..ops.pool import cross_entropy
+    from ..parallel import hvd
+    data = open_data(args, dev, world, rank, "val")    # sets args.num_classes
+    model = build_model(args, dev).eval()
+    loader = make_loader(args, dev, rank, model, data, train=False)
+    s2d = loader.layout == "s2d"
+    meta = data[2]
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def sync():
+        if dev.type == "cuda":
+            torch.cuda.synchronize()
+
+    def step():
+        with torch.no_grad():
+            x, y = loader.next()
+            with torch.autocast(device_type=dev.type, dtype=amp, enabled=amp is not None,
+                                cache_enabled=False):
+                logits = model(x, s2d=True) if s2d else model(x)
+            return cross_entropy(logits, y, ignore_index=-100,
+                                 label_smoothing=args.label_smoothing, stats=stats)
+
+    if rank == 0:
+        print(f"Model: {args.model}  Batch size: {args.batch_size} per device, "
+              f"{args.batch_size * world} global  Devices: {world} x {dev.type}  "
+              f"Data: {data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size})  "
+              f"dtype: {args.dtype}  mode: eval", flush=True)
+    for i in range(min(args.num_warmup_batches, loader.steps_per_epoch)):
+        step()
+    loader.new_epoch()           # the counted pass starts at row 0
+    sync()
+    if world > 1:
+        torch.distributed.barrier()
+    base = stats.tolist()
+    steps = loader.steps_per_epoch
+    t0 = time.perf_counter()
+    loss = None
+    for i in range(1, steps + 1):
+        loss = step()
+        heartbeat.beat(i)
+        if rank == 0 and (i % args.display_every == 0 or i == steps):
+            print(f"{i}\tloss {float(loss):.3f}", flush=True)
+    sync()
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    counts = global_counts(stats, base, world)
+    total = counts[0] / elapsed
+    if rank == 0:
+        kept = max(counts[0], 1)
+        print("-" * 64)
+        print(f"total images/sec: {total:.2f}")
+        print("-" * 64)
+        print("Accuracy @ 1 = %.4f Accuracy @ 5 = %.4f [%d examples]"
+              % (counts[1] / kept, counts[2] / kept, counts[0]), flush=True)
+        if args.json:
+            res = {"model": args.model, "images_per_s": round(total, 2),
+                   "ms_per_step": round(elapsed / steps * 1e3, 3),
+                   "batch_per_device": args.batch_size, "devices": world, "dtype": args.dtype,
+                   "exec": "eval", "final_loss": round(float(loss), 4), "data": data[3],
+                   "images": meta["n"], "layout": loader.layout, "kept": counts[0]}
             res.update(accuracy_fields(counts))
             print(json.dumps(res), flush=True)
     hvd.shutdown()

@@ -25,7 +25,8 @@ import torch
 from torch import nn
 
 from ..ops.batchnorm import BatchNormAct2d, ResidualMask, bn_relu_maxpool
-from ..ops.conv import BNGradLink, Conv2dNHWC, GradJoin, StemConv2d, WeightFlipper
+from ..ops.conv import (BNGradLink, Conv2dNHWC, GradJoin, StemConv2d, WeightFlipper,
+                        stem_takes_s2d)
 from ..ops.pool import MaxPool2dNHWC, global_avg_pool
 
 # Downsample blocks build their shortcut after the main path (see Bottleneck.forward; A/B switch,
@@ -122,9 +123,17 @@ class ResNet(nn.Module):
         # every stride-1 conv weight flipped for its backward-data pass in one launch per step
         self._flipper = WeightFlipper(list(self.layers.modules()))
 
-    def forward(self, x):
+    def takes_s2d(self, device, dtype) -> bool:
+        """Whether ``forward(z, s2d=True)`` is available on ``device`` computing in ``dtype``
+        (``ops.conv.stem_takes_s2d``); otherwise feed the model ``nhwc`` images."""
+        return stem_takes_s2d(self.stem[0], device, dtype)
+
+    def forward(self, x, s2d: bool = False):
+        """``s2d=True``: ``x`` is the stem's space-to-depth tensor ``z`` (bf16 ``[N, 16, H/2,
+        W/2]``, as ``DeviceImageLoader(layout="s2d")`` writes it), not the image batch."""
         with self._flipper.scope():
-            y, st = self.stem[0].forward_stats(x)    # epilogue BN statistics, as in the blocks
+            # epilogue BN statistics, as in the blocks
+            y, st = self.stem[0].forward_s2d(x) if s2d else self.stem[0].forward_stats(x)
             # BN + ReLU + max pool as one pass each way when the statistics come summed
             x = bn_relu_maxpool(self.stem[1], self.stem[2], y, st)
             link = None

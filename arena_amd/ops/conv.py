@@ -325,6 +325,16 @@ def stem_ok(x: Tensor, w: Tensor, stride: int, pad: int) -> bool:
             and x.shape[3] % 2 == 0 and not x.requires_grad)
 
 
+def stem_takes_s2d(conv, device, dtype) -> bool:
+    """Whether stem convolution ``conv`` on ``device`` computing in ``dtype`` consumes the
+    space-to-depth tensor (``StemConv2d.forward_s2d``); when it does not, ask the image loader
+    for its ``nhwc`` layout and call the module as usual."""
+    return (torch.device(device).type == "cuda" and dtype == torch.bfloat16
+            and isinstance(conv, StemConv2d) and tuple(conv.kernel_size) == (7, 7)
+            and conv.stride[0] == 2 and conv.padding[0] == 3 and conv.in_channels == 3
+            and conv.out_channels % 64 == 0 and _mode() not in ("off", MIOPEN))
+
+
 class BNGradLink:
     """A BatchNorm layer whose output is the input of a convolution: the conv's backward-data
     pass produces exactly the gradient the BN's backward starts from, so its epilogue also
@@ -994,9 +1004,32 @@ class StemConv2d(Conv2dNHWC):
         if not ok or not stem_ok(xin, w, s, p):
             return super().forward_stats(x, want_stats, join, bn_link)
         xin = xin.contiguous(memory_format=torch.channels_last)
-        want = want_stats and torch.is_grad_enabled() and self.training
         with torch.autocast("cuda", enabled=False):
             z = _ext.load().s2d_stem(xin)
+        return self.forward_s2d(z, want_stats)
+
+    def forward_s2d(self, z: Tensor, want_stats: bool = True):
+        """``forward_stats`` from the space-to-depth tensor on: ``z`` is what ``s2d_stem`` makes of
+        the image batch, channels_last bf16 ``[N, 16, H/2, W/2]`` (``DeviceImageLoader`` writes it
+        straight from the uint8 dataset). There is no other path from ``z``: a module or mode that
+        does not take it (``stem_takes_s2d``) is an error, not a fallback."""
+        w = self.weight
+        amp = torch.is_autocast_enabled("cuda") and \
+            torch.get_autocast_dtype("cuda") == torch.bfloat16
+        if not z.is_cuda or _mode() in ("off", MIOPEN) or self.out_channels % 64 \
+                or tuple(self.kernel_size) != (7, 7) or self.stride[0] != 2 \
+                or self.padding[0] != 3 or self.in_channels > 4:
+            raise RuntimeError("StemConv2d.forward_s2d: this stem / ARENA_CONV mode does not take "
+                               "the space-to-depth input (see stem_takes_s2d)")
+        if z.dtype != torch.bfloat16 or z.dim() != 4 or z.shape[1] != 16 \
+                or not z.is_contiguous(memory_format=torch.channels_last) or z.requires_grad:
+            raise ValueError("forward_s2d: z must be channels_last bf16 [N, 16, H/2, W/2] "
+                             "without a gradient")
+        if w.dtype != torch.bfloat16 and not (amp and w.dtype == torch.float32):
+            raise ValueError("forward_s2d: a bf16 weight, or an fp32 weight under bf16 autocast")
+        fuse = _STEM_FUSED
+        want = want_stats and torch.is_grad_enabled() and self.training
+        with torch.autocast("cuda", enabled=False):
             w16 = _StemWeightFn.apply(w) if fuse else stem_weight(w.to(torch.bfloat16))
             fv, wcfg = _stem_plan(z, w16)
             y, part = _StemFn.apply(z, w16, want, fv, wcfg)

@@ -291,3 +291,97 @@ def shard_sgd(grad, w32, mom, wbf, lr, momentum, weight_decay, scale):
     w32.sub_(lr * mom)
     if wbf is not None:
         wbf.copy_(w32)
+
+
+# ------------------------------------------------------------------------------------------------
+# Device-resident image pipeline (csrc/ops/data_kernels.hip). Everything the kernel and this
+# reference must agree on is defined once, here:
+#
+# * rows: ``pos = cursor * B + r``; training takes ``perm[pos % L]``; evaluation takes
+#   ``perm[pos]`` while ``pos < L`` and pads the rest (zero image, label IMAGE_PAD_LABEL, row -1).
+#   A permutation entry outside ``[0, n)`` is padding too.
+# * the hash: ``image_hash(seed, stream, pos, k) = hash4(seed, stream * 4 + k, pos & 0xFFFFFFFF,
+#   pos >> 32)`` for draw k (0: y0, 1: x0, 2: flip) -- a function of (seed, stream, pos) alone.
+# * uniform to range: ``uniform_below(h, m) = (h * m) >> 32`` (the high word of the product), so
+#   ``y0 = uniform_below(h0, S - Hc + 1)``, ``x0 = uniform_below(h1, S - Wc + 1)``, ``flip = h2 >>
+#   31``. Evaluation: the centre crop ``((S - Hc) // 2, (S - Wc) // 2)``, no flip.
+# * the table: ``image_table(mean, std, dtype)[c][u] = ((u / 255 - mean[c]) / std[c])`` computed
+#   in fp32 on the host and rounded once to ``dtype``; both sides only look values up.
+# * the space-to-depth channel: ``s2d_channel(dy, dx, c) = (dy * 2 + dx) * 3 + c``, channels
+#   12..15 zero, ``z[n][ch][i][j] = x[n][c][2i + dy][2j + dx]`` (the order of ``s2d_stem``).
+# ------------------------------------------------------------------------------------------------
+IMAGE_PAD_LABEL = -100
+
+
+def image_hash(seed: int, stream: int, pos: torch.Tensor, k: int) -> torch.Tensor:
+    pos = pos.to(torch.int64)
+    return hash4(seed, (stream * 4 + k) & _M32, pos & _M32, (pos >> 32) & _M32)
+
+
+def uniform_below(h: torch.Tensor, m: int) -> torch.Tensor:
+    """uint32 hash -> integer in [0, m), m <= 2**16 (the product stays inside int64)."""
+    return (h * m) >> 32
+
+
+def image_crop_draws(pos: torch.Tensor, S: int, Hc: int, Wc: int, train: bool, seed: int,
+                     stream: int):
+    """(y0, x0, flip) int64 tensors for batch positions ``pos``."""
+    if not train:
+        one = torch.ones_like(pos, dtype=torch.int64)
+        return one * ((S - Hc) // 2), one * ((S - Wc) // 2), one * 0
+    return (uniform_below(image_hash(seed, stream, pos, 0), S - Hc + 1),
+            uniform_below(image_hash(seed, stream, pos, 1), S - Wc + 1),
+            image_hash(seed, stream, pos, 2) >> 31)
+
+
+def image_table(mean, std, dtype=torch.float32) -> torch.Tensor:
+    """[3, 256] lookup table of ``(u / 255 - mean[c]) / std[c]`` (fp32 arithmetic, one rounding)."""
+    m = torch.tensor([float(v) for v in mean], dtype=torch.float32).view(3, 1)
+    s = torch.tensor([float(v) for v in std], dtype=torch.float32).view(3, 1)
+    u = torch.arange(256, dtype=torch.float32).view(1, 256)
+    return ((u / 255.0 - m) / s).to(dtype).contiguous()
+
+
+def s2d_channel(dy: int, dx: int, c: int) -> int:
+    return (dy * 2 + dx) * 3 + c
+
+
+def image_batch(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out, crop_h,
+                crop_w, train, seed, stream, layout, advance):
+    """CPU twin of ``arena_image_batch`` (same arguments as the extension's ``image_batch``)."""
+    n, S = images.shape[0], images.shape[1]
+    B, L, Hc, Wc = out.shape[0], perm.numel(), int(crop_h), int(crop_w)
+    if Hc % 2 or Wc % 2 or not (2 <= Hc <= S and 2 <= Wc <= S):
+        raise ValueError("image_batch: the crop must be even and at most the stored size")
+    if table.dtype != out.dtype or tuple(table.shape) != (3, 256):
+        raise ValueError("image_batch: table must be [3, 256] in out's dtype")
+    pos = _cursor_val(cursor, 0) * B + torch.arange(B, dtype=torch.int64)
+    p64 = perm.to(torch.int64)
+    if train:
+        row = p64[pos % L]
+    else:
+        row = torch.where(pos < L, p64[pos.clamp(max=L - 1)], torch.full_like(pos, -1))
+    valid = (row >= 0) & (row < n)
+    row = torch.where(valid, row, torch.full_like(row, -1))
+    y0, x0, flip = image_crop_draws(pos, S, Hc, Wc, bool(train), int(seed) & _M32, int(stream))
+    xo = torch.arange(Wc, dtype=torch.int64).view(1, Wc)
+    ys = y0.view(B, 1) + torch.arange(Hc, dtype=torch.int64).view(1, Hc)
+    xs = x0.view(B, 1) + torch.where(flip.view(B, 1) != 0, Wc - 1 - xo, xo)
+    px = images[row.clamp(min=0).view(B, 1, 1), ys.view(B, Hc, 1), xs.view(B, 1, Wc)]
+    val = table[torch.arange(3).view(1, 1, 1, 3), px.to(torch.int64)]       # [B, Hc, Wc, 3]
+    val = torch.where(valid.view(B, 1, 1, 1), val, torch.zeros_like(val))
+    if layout == 1:
+        out.copy_(val.permute(0, 3, 1, 2))
+    else:
+        z = torch.zeros(B, Hc // 2, Wc // 2, 16, dtype=val.dtype)
+        for dy in range(2):
+            for dx in range(2):
+                ch = s2d_channel(dy, dx, 0)
+                z[..., ch:ch + 3] = val[:, dy::2, dx::2, :]
+        out.copy_(z.permute(0, 3, 1, 2))
+    labels_out.copy_(torch.where(valid, labels.to(torch.int64)[row.clamp(min=0)],
+                                 torch.full_like(row, IMAGE_PAD_LABEL)))
+    rows_out.copy_(row)
+    crop_out.view(B, 3).copy_(torch.stack([y0, x0, flip], dim=1))
+    if advance:
+        cursor.add_(1)

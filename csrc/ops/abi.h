@@ -155,6 +155,26 @@ struct ArenaConvWgradVariant {
   int c16;
 };
 
+// One batch of the device-resident image pipeline (csrc/ops/data_kernels.hip).
+struct ArenaImageBatch {
+  const uint8_t* images;    // [n][S][S][3] uint8
+  const long long* labels;  // [n]
+  long long n;
+  const int* perm;          // [L] dataset rows, each in [0, n)
+  long long L;
+  long long* cursor;        // device counter of completed batches (read; += 1 when advancing)
+  const void* table;        // [3][256] normalised values in the output dtype
+  void* out;                // z [B][Hc/2][Wc/2][16] bf16, or x [B][Hc][Wc][3] bf16 / fp32
+  long long* labels_out;    // [B]
+  int* rows_out;            // [B]
+  int* crop_out;            // [B][3]: y0, x0, flip
+  int S, B, Hc, Wc;
+  int train;                // 1: shuffled rows (wrapping), random crop + flip; 0: in order,
+                            // centre crop, rows past L are padding
+  uint32_t seed;
+  int stream;               // draw stream (the data-parallel rank)
+};
+
 // Intra-node xGMI collective (csrc/ccl/xgmi_ccl.hip): every rank's registered buffers, mapped into
 // this process through hipIpc handles (buf[rank] / sig[rank] are the local allocations).
 #define ARENA_CCL_MAX_RANKS 8
@@ -309,6 +329,10 @@ hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* d
                                float* dw_f32, int N, int H, int W, int C, int Cout, int R, int S,
                                int stride, int pad_h, int pad_w, int Ho, int Wo, int c16,
                                int variant, int splits_hint, float scale, hipStream_t st);
+
+// csrc/ops/data_kernels.hip
+hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f32, int advance,
+                             hipStream_t st);
 
 // csrc/ccl/xgmi_ccl.hip
 hipError_t arena_ccl_malloc(void** p, size_t bytes, int uncached);

@@ -1458,6 +1458,80 @@ Tensor s2d_stem(Tensor x) {
   return z;
 }
 
+// One batch of the device-resident image pipeline (data_kernels.hip; semantics in
+// ops/reference.py image_batch). images uint8 [n, S, S, 3], labels int64 [n], perm int32 [L]
+// (every entry a row of images: checked by the loader when it installs a permutation; the kernel
+// turns a stray one into a padding row), cursor int64 [1], table [3, 256] in out's dtype.
+// layout 0: out = z, bf16 channels_last [B, 16, crop_h/2, crop_w/2]; 1: out = x, bf16 or fp32
+// channels_last [B, 3, crop_h, crop_w]. labels_out int64 [B], rows_out int32 [B], crop_out int32
+// [B, 3]. advance: the cursor += 1 on the stream after the batch kernel.
+void image_batch(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table, Tensor out,
+                 Tensor labels_out, Tensor rows_out, Tensor crop_out, int64_t crop_h,
+                 int64_t crop_w, bool train, int64_t seed, int64_t stream, int64_t layout,
+                 bool advance) {
+  for (auto* t : {&images, &labels, &perm, &cursor, &table, &labels_out, &rows_out, &crop_out})
+    check_dev(*t, "image_batch operand");
+  TORCH_CHECK(out.is_cuda(), "image_batch: out must be a GPU tensor");
+  for (auto* t : {&labels, &perm, &cursor, &table, &out, &labels_out, &rows_out, &crop_out})
+    TORCH_CHECK(t->device() == images.device(), "image_batch: all tensors on one GPU");
+  TORCH_CHECK(images.scalar_type() == torch::kUInt8 && images.dim() == 4 && images.size(3) == 3 &&
+                  images.size(1) == images.size(2) && images.size(0) >= 1,
+              "image_batch: images must be uint8 [n, S, S, 3]");
+  const int64_t n = images.size(0), S = images.size(1), L = perm.numel();
+  TORCH_CHECK(S >= 2 && S <= 16384, "image_batch: stored size must lie in [2, 16384]");
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.dim() == 1 && labels.size(0) == n,
+              "image_batch: labels must be int64 [n]");
+  TORCH_CHECK(perm.scalar_type() == torch::kInt32 && perm.dim() == 1 && L >= 1,
+              "image_batch: perm must be a non-empty int32 vector");
+  TORCH_CHECK(cursor.scalar_type() == torch::kInt64 && cursor.numel() == 1,
+              "image_batch: cursor must be one int64");
+  TORCH_CHECK(layout == 0 || layout == 1, "image_batch: layout 0 (s2d) or 1 (nhwc)");
+  TORCH_CHECK(crop_h >= 2 && crop_w >= 2 && crop_h % 2 == 0 && crop_w % 2 == 0 && crop_h <= S &&
+                  crop_w <= S,
+              "image_batch: the crop must be even and at most the stored size");
+  const bool f32 = out.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(out.dim() == 4 && out.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  (out.scalar_type() == torch::kBFloat16 || (f32 && layout == 1)),
+              "image_batch: out must be channels_last bf16 (or fp32 for nhwc)");
+  const int64_t B = out.size(0);
+  TORCH_CHECK(B >= 1 && B <= 65535, "image_batch: batch must lie in [1, 65535]");
+  if (layout == 0) {
+    TORCH_CHECK(out.size(1) == 16 && out.size(2) == crop_h / 2 && out.size(3) == crop_w / 2,
+                "image_batch: z must be [B, 16, crop_h / 2, crop_w / 2]");
+  } else {
+    TORCH_CHECK(out.size(1) == 3 && out.size(2) == crop_h && out.size(3) == crop_w,
+                "image_batch: x must be [B, 3, crop_h, crop_w]");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "image_batch: out must be 16-byte aligned");
+  TORCH_CHECK(table.scalar_type() == out.scalar_type() && table.dim() == 2 && table.size(0) == 3 &&
+                  table.size(1) == 256,
+              "image_batch: table must be [3, 256] in out's dtype");
+  TORCH_CHECK(labels_out.scalar_type() == torch::kInt64 && labels_out.numel() == B &&
+                  rows_out.scalar_type() == torch::kInt32 && rows_out.numel() == B &&
+                  crop_out.scalar_type() == torch::kInt32 && crop_out.numel() == 3 * B,
+              "image_batch: labels_out int64 [B], rows_out int32 [B], crop_out int32 [B, 3]");
+  TORCH_CHECK(stream >= 0 && stream < (1 << 30), "image_batch: stream must lie in [0, 2^30)");
+  ArenaImageBatch a{};
+  a.images = images.data_ptr<uint8_t>();
+  a.labels = reinterpret_cast<const long long*>(labels.data_ptr<int64_t>());
+  a.n = n;
+  a.perm = perm.data_ptr<int>();
+  a.L = L;
+  a.cursor = reinterpret_cast<long long*>(cursor.data_ptr<int64_t>());
+  a.table = table.data_ptr();
+  a.out = out.data_ptr();
+  a.labels_out = reinterpret_cast<long long*>(labels_out.data_ptr<int64_t>());
+  a.rows_out = rows_out.data_ptr<int>();
+  a.crop_out = crop_out.data_ptr<int>();
+  a.S = (int)S; a.B = (int)B; a.Hc = (int)crop_h; a.Wc = (int)crop_w;
+  a.train = train ? 1 : 0;
+  a.seed = (uint32_t)seed;
+  a.stream = (int)stream;
+  check_hip(arena_image_batch(a, (int)layout, f32 ? 1 : 0, advance ? 1 : 0, cur_stream()),
+            "image_batch");
+}
+
 // The 7x7 stem weight [Cout, C<=4, 7, 7] (fp32 or bf16, any strides) -> its space-to-depth form,
 // channels_last bf16 [Cout, 16, 4, 4] (ops/conv.py stem_weight).
 Tensor stem_weight(Tensor w) {
@@ -1844,6 +1918,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_phases", &conv_dgrad_phases, py::arg("dy"), py::arg("wps"), py::arg("geom"),
         py::arg("dx_out"), py::arg("addend"), py::arg("stride"), py::arg("variant"));
   m.def("s2d_stem", &s2d_stem);
+  m.def("image_batch", &image_batch);
   m.def("stem_weight", &stem_weight);
   m.def("stem_weight_grad", &stem_weight_grad);
   m.def("bn_bwd", &bn_bwd, py::arg("dy"), py::arg("mask"), py::arg("x"), py::arg("mean"),

@@ -1,0 +1,150 @@
+// Device-resident image input pipeline (gfx950): one kernel turns rows of an HBM-resident uint8
+// dataset [n][S][S][3] into the training batch the stem consumes -- gather (device permutation +
+// device cursor), random crop, horizontal flip, normalisation, bf16 rounding and the stem's
+// space-to-depth rearrangement in one pass over the batch's bytes. The fp32 image batch never
+// exists. The CPU twin is arena_amd/ops/reference.py image_batch (bit for bit).
+//
+//   pos = cursor[0] * B + r                                  (batch row r)
+//   training:   row = perm[pos % L]
+//   evaluation: row = perm[pos] while pos < L, else padding (zero image, label -100, row -1)
+//   training:   y0 = draw(0, S - Hc + 1), x0 = draw(1, S - Wc + 1), flip = hash(2) >> 31 with
+//               hash(k) = hash4(seed, stream * 4 + k, low32(pos), high32(pos)) (common.h) and
+//               draw(k, m) = (hash(k) * m) >> 32: functions of (seed, stream, pos) alone, so a
+//               resumed run and a replayed graph draw the same values
+//   evaluation: the centre crop, y0 = (S - Hc) / 2, x0 = (S - Wc) / 2, no flip
+//   out pixel (y, x, c) = table[c][img[row][y0 + y][x0 + (flip ? Wc - 1 - x : x)][c]]
+// table is 3 x 256 values of the output dtype, built once on the host from mean and std, so the
+// kernel and the reference cannot round differently.
+#include "common.h"
+
+namespace {
+
+struct ImageRow {
+  long long row;   // dataset row, -1: padding
+  int y0, x0, flip;
+};
+
+// The same for every thread of a block (blockIdx.y is the batch row): scalar work.
+__device__ __forceinline__ ImageRow image_row(const ArenaImageBatch& a, int r) {
+  ImageRow o;
+  const unsigned long long pos = (unsigned long long)a.cursor[0] * (unsigned long long)a.B + r;
+  const unsigned long long L = (unsigned long long)a.L;
+  if (a.train) {
+    o.row = a.perm[pos % L];
+    const uint32_t lo = (uint32_t)pos, hi = (uint32_t)(pos >> 32);
+    const uint32_t st = (uint32_t)a.stream * 4u;
+    o.y0 = (int)__umulhi(arena::hash4(a.seed, st + 0u, lo, hi), (uint32_t)(a.S - a.Hc + 1));
+    o.x0 = (int)__umulhi(arena::hash4(a.seed, st + 1u, lo, hi), (uint32_t)(a.S - a.Wc + 1));
+    o.flip = (int)(arena::hash4(a.seed, st + 2u, lo, hi) >> 31);
+  } else {
+    o.row = pos < L ? (long long)a.perm[pos] : -1;
+    o.y0 = (a.S - a.Hc) >> 1;
+    o.x0 = (a.S - a.Wc) >> 1;
+    o.flip = 0;
+  }
+  // a permutation entry outside the dataset reads nothing: the row becomes padding
+  if (o.row < 0 || o.row >= a.n) o.row = -1;
+  return o;
+}
+
+// One thread per 2x2 pixel quad (i, j) of one batch row: two source runs of 6 bytes (rows
+// 2i, 2i+1; pixels 2j, 2j+1), read bytewise because x0 is arbitrary.
+//   LAYOUT 0 (s2d): z[b][i][j][(dy*2+dx)*3 + c], channels 12..15 zero: two 16-byte stores, the
+//                   channel order of s2d_stem_kernel (conv_kernels.hip)
+//   LAYOUT 1 (nhwc): x[b][2i+dy][2j+dx][c]: per dy the quad's 6 values are contiguous, stored
+//                   as three 4-byte (bf16) or 8-byte (fp32) words, aligned because Wc is even
+template <typename T, int LAYOUT>
+__global__ __launch_bounds__(256) void image_batch_kernel(const ArenaImageBatch a) {
+  __shared__ T tab[3 * 256];
+  for (int e = threadIdx.x; e < 3 * 256; e += 256) tab[e] = ((const T*)a.table)[e];
+  const int b = blockIdx.y;
+  const ImageRow ir = image_row(a, b);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.labels_out[b] = ir.row >= 0 ? a.labels[ir.row] : -100ll;
+    a.rows_out[b] = (int)ir.row;
+    a.crop_out[3 * b + 0] = ir.y0;
+    a.crop_out[3 * b + 1] = ir.x0;
+    a.crop_out[3 * b + 2] = ir.flip;
+  }
+  __syncthreads();
+  const int Hz = a.Hc >> 1, Wz = a.Wc >> 1;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= Hz * Wz) return;
+  const int i = q / Wz, j = q - i * Wz;
+  T v[12];   // [dy][dx][c]
+  if (ir.row >= 0) {
+    // the row's byte offset is 64-bit (n * S * S * 3 passes 2^31 at 10923 images of 256^2);
+    // offsets inside one image fit 32 bits (S <= 16384, checked by the launcher)
+    const uint8_t* img = a.images + (size_t)ir.row * ((size_t)a.S * a.S * 3);
+    const int xa = ir.flip ? ir.x0 + a.Wc - 1 - 2 * j : ir.x0 + 2 * j;   // source of dx = 0
+    const int xb = ir.flip ? xa - 1 : xa + 1;                            // source of dx = 1
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const uint32_t rowoff = (uint32_t)(ir.y0 + 2 * i + dy) * (uint32_t)a.S;
+      const uint8_t* pa = img + (rowoff + (uint32_t)xa) * 3u;
+      const uint8_t* pb = img + (rowoff + (uint32_t)xb) * 3u;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[dy * 6 + c] = tab[c * 256 + pa[c]];
+        v[dy * 6 + 3 + c] = tab[c * 256 + pb[c]];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = (T)0;
+  }
+  if constexpr (LAYOUT == 0) {
+    static_assert(sizeof(T) == 2, "the space-to-depth tensor is bf16");
+    uint4 o0, o1;
+    o0.x = v[0] | ((uint32_t)v[1] << 16); o0.y = v[2] | ((uint32_t)v[3] << 16);
+    o0.z = v[4] | ((uint32_t)v[5] << 16); o0.w = v[6] | ((uint32_t)v[7] << 16);
+    o1.x = v[8] | ((uint32_t)v[9] << 16); o1.y = v[10] | ((uint32_t)v[11] << 16);
+    o1.z = 0u; o1.w = 0u;
+    uint4* dst = reinterpret_cast<uint4*>((uint16_t*)a.out + ((size_t)b * Hz * Wz + q) * 16);
+    dst[0] = o0;
+    dst[1] = o1;
+  } else {
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const size_t e = (((size_t)b * a.Hc + 2 * i + dy) * a.Wc + 2 * j) * 3;
+      if constexpr (sizeof(T) == 2) {
+        uint32_t* dst = reinterpret_cast<uint32_t*>((uint16_t*)a.out + e);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          dst[k] = (uint32_t)v[dy * 6 + 2 * k] | ((uint32_t)v[dy * 6 + 2 * k + 1] << 16);
+      } else {
+        float2* dst = reinterpret_cast<float2*>((float*)a.out + e);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dst[k] = make_float2(v[dy * 6 + 2 * k], v[dy * 6 + 2 * k + 1]);
+      }
+    }
+  }
+}
+
+// A launch of its own, in stream order after the batch kernel: no block of that launch can see
+// the advanced cursor.
+__global__ void image_cursor_kernel(long long* cursor) { cursor[0] += 1; }
+
+}  // namespace
+
+// layout 0: space-to-depth z (bf16), 1: nhwc; out_f32: the nhwc output (and the table) is fp32,
+// else bf16. advance: add 1 to the device cursor after the batch is written.
+extern "C" hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f32, int advance,
+                                        hipStream_t st) {
+  if (a.B < 1 || a.B > 65535 || a.n < 1 || a.L < 1 || a.S < 2 || a.S > 16384 || a.Hc < 2 ||
+      a.Wc < 2 || (a.Hc & 1) || (a.Wc & 1) || a.Hc > a.S || a.Wc > a.S || a.stream < 0 ||
+      a.stream >= (1 << 30) || layout < 0 || layout > 1 || (layout == 0 && out_f32))
+    return hipErrorInvalidValue;
+  const int quads = (a.Hc / 2) * (a.Wc / 2);
+  const dim3 g((unsigned)((quads + 255) / 256), (unsigned)a.B);
+  if (layout == 0)
+    hipLaunchKernelGGL((image_batch_kernel<uint16_t, 0>), g, dim3(256), 0, st, a);
+  else if (out_f32)
+    hipLaunchKernelGGL((image_batch_kernel<float, 1>), g, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((image_batch_kernel<uint16_t, 1>), g, dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !advance) return e;
+  hipLaunchKernelGGL(image_cursor_kernel, dim3(1), dim3(1), 0, st, a.cursor);
+  return hipGetLastError();
+}
