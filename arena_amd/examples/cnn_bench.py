@@ -13,7 +13,11 @@ This is the same workload, built for MI355X:
 * output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``;
 * by default one static random batch; with ``--data_dir`` / ``--synth_images`` a uint8 dataset
   resident in GPU memory, fed by one kernel at the head of every (captured) step
-  (``arena_amd.ops.data.DeviceImageLoader``), with epochs and an ``--eval`` pass over ``val``.
+  (``arena_amd.ops.data.DeviceImageLoader``), with epochs and an ``--eval`` pass over ``val``;
+* tf_cnn_benchmarks' learning-rate flags (piecewise schedule, warm-up epochs, exponential
+  staircase). The schedule advances on the device at the head of every step
+  (``arena_amd.ops.schedule.DeviceLR``), inside the captured graph, and counts the measured steps:
+  it is set back to step 0 where epoch 1 starts, after the warm-up batches.
 
     arena submit mpijob --name r50 --workers 8 --gpus 1 \\
         "python -m arena_amd.examples.cnn_bench --model resnet50 --batch_size 128"
@@ -44,6 +48,20 @@ def parse(argv=None):
     ap.add_argument("--num_warmup_batches", type=int, default=10)
     ap.add_argument("--display_every", type=int, default=10)
     ap.add_argument("--learning_rate", type=float, default=0.1)
+    ap.add_argument("--piecewise_learning_rate_schedule", default=None, metavar="LR0;E1;LR1;...",
+                    help="learning rate LR0 until epoch E1, LR1 until E2, ... (tf_cnn_benchmarks' "
+                         "flag), e.g. '0.4;30;0.04;60;0.004;80;0.0004'")
+    ap.add_argument("--num_learning_rate_warmup_epochs", type=float, default=0.0,
+                    help="ramp the learning rate linearly from 0 to its first value over this "
+                         "many epochs")
+    ap.add_argument("--init_learning_rate", type=float, default=None,
+                    help="first value of the exponential staircase (default: --learning_rate)")
+    ap.add_argument("--num_epochs_per_decay", type=float, default=0.0,
+                    help="exponential staircase: multiply the learning rate by "
+                         "--learning_rate_decay_factor every this many epochs")
+    ap.add_argument("--learning_rate_decay_factor", type=float, default=0.0)
+    ap.add_argument("--minimum_learning_rate", type=float, default=0.0,
+                    help="lower bound of the exponential staircase")
     ap.add_argument("--momentum", type=float, default=0.9)
     ap.add_argument("--weight_decay", type=float, default=4e-5)
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
@@ -103,7 +121,56 @@ def parse(argv=None):
         ap.error("--data_dir and --synth_images exclude each other")
     if (args.num_epochs or args.stored_size) and not has_data(args):
         ap.error("--num_epochs / --stored_size need --data_dir or --synth_images")
+    expo = (args.init_learning_rate is not None or args.num_epochs_per_decay
+            or args.learning_rate_decay_factor or args.minimum_learning_rate)
+    if args.piecewise_learning_rate_schedule is not None and expo:
+        ap.error("--piecewise_learning_rate_schedule excludes --init_learning_rate, "
+                 "--num_epochs_per_decay, --learning_rate_decay_factor and "
+                 "--minimum_learning_rate")
+    if bool(args.num_epochs_per_decay) != bool(args.learning_rate_decay_factor) or (
+            args.minimum_learning_rate and not args.num_epochs_per_decay):
+        ap.error("the exponential schedule needs --num_epochs_per_decay and "
+                 "--learning_rate_decay_factor together")
+    if args.num_learning_rate_warmup_epochs < 0:
+        ap.error("--num_learning_rate_warmup_epochs must be >= 0")
+    if has_schedule(args) and args.eval:
+        ap.error("the learning-rate flags do not apply to --eval")
     return args
+
+
+IMAGENET_TRAIN_IMAGES = 1281167    # tf_cnn_benchmarks' epoch when no dataset defines one
+
+
+def has_schedule(args) -> bool:
+    """True if any learning-rate schedule flag was given (a plain ``--learning_rate`` is not one)."""
+    return (getattr(args, "piecewise_learning_rate_schedule", None) is not None
+            or getattr(args, "init_learning_rate", None) is not None
+            or bool(getattr(args, "num_learning_rate_warmup_epochs", 0))
+            or bool(getattr(args, "num_epochs_per_decay", 0)))
+
+
+def schedule_segments(args, steps_per_epoch: float, total_steps: int):
+    """The segments the schedule flags describe (None without any), as tf_cnn_benchmarks reads
+    them. ``steps_per_epoch``: the dataset's, else ImageNet's size over the global batch."""
+    if not has_schedule(args):
+        return None
+    from ..ops import schedule
+    try:
+        if args.piecewise_learning_rate_schedule is not None:
+            segs = schedule.piecewise(args.piecewise_learning_rate_schedule, steps_per_epoch)
+        else:
+            init = (args.learning_rate if args.init_learning_rate is None
+                    else args.init_learning_rate)
+            if args.num_epochs_per_decay:
+                segs = schedule.exponential(init, args.num_epochs_per_decay,
+                                            args.learning_rate_decay_factor,
+                                            args.minimum_learning_rate, steps_per_epoch,
+                                            total_steps)
+            else:
+                segs = schedule.constant(init)
+        return schedule.with_warmup(segs, args.num_learning_rate_warmup_epochs, steps_per_epoch)
+    except ValueError as e:
+        raise SystemExit(f"learning-rate schedule: {e}")
 
 
 def has_data(args) -> bool:
@@ -176,8 +243,11 @@ def synthetic_batch(args, dev):
     return x, y
 
 
-def build(args, dev, world):
-    """Model, optimizer (wrapped for DP) and one synthetic batch, ready to step."""
+def build(args, dev, world, segments=None):
+    """Model, optimizer (wrapped for DP) and one synthetic batch, ready to step. ``segments``: a
+    learning-rate schedule (``schedule_segments``). The master-weight optimizers then read a
+    ``DeviceLR`` (``schedule_of(opt)``) in every update kernel; the other paths keep their float
+    ``lr`` and the caller sets it on the host each step."""
     from ..parallel import hvd
     model = build_model(args, dev)
     decay, no_decay = [], []
@@ -190,6 +260,11 @@ def build(args, dev, world):
     if master and (getattr(args, "dtype", "bf16") != "bf16" or dev.type != "cuda"):
         raise SystemExit("--master_weights on needs --dtype bf16 on a GPU (the weights become "
                          "bf16 and the update runs in the HIP multi-tensor kernel)")
+    sched = None
+    if segments is not None and master:
+        from ..ops.schedule import DeviceLR
+        sched = DeviceLR(segments, dev)
+    lr = args.learning_rate if sched is None else sched
     opt = None
     if master and world > 1:
         # data parallel keeps the bf16-weight design: ShardedMasterSGD over the xGMI kernels
@@ -200,13 +275,19 @@ def build(args, dev, world):
         opt = ShardedMasterSGD(
             [{"params": decay, "weight_decay": args.weight_decay},
              {"params": no_decay, "weight_decay": 0.0, "weights": "fp32"}],
-            lr=args.learning_rate, momentum=args.momentum, bucket_mb=args.bucket_mb,
+            lr=lr, momentum=args.momentum, bucket_mb=args.bucket_mb,
             backend=comm, order=list(model.parameters()))
         if hvd.rank() == 0 and opt.backend != "xgmi" and comm == "auto":
             print(f"[rank 0] ShardedMasterSGD over RCCL, {opt.backend} (ranks cannot map each "
                   "other's GPUs)", file=sys.stderr, flush=True)
     if opt is not None:
         pass                   # data parallel, sharded
+    elif master and sched is not None:
+        # as below, with the BN / bias group on the multi-tensor kernel that reads the device lr
+        from ..ops.optim import MasterSGD, MultiTensorSGD32, OptimizerGroup
+        opt = OptimizerGroup(
+            MasterSGD(decay, lr=sched, momentum=args.momentum, weight_decay=args.weight_decay),
+            MultiTensorSGD32(no_decay, lr=sched, momentum=args.momentum))
     elif master:
         # conv/fc weights live in bf16 (fp32 masters inside MasterSGD): no per-step casts
         from ..ops.optim import MasterSGD, OptimizerGroup
@@ -230,6 +311,17 @@ def build(args, dev, world):
     return model, opt, x, y
 
 
+def schedule_of(opt):
+    """The ``DeviceLR`` an optimizer's update kernels read (None: float learning rates)."""
+    from ..ops.schedule import DeviceLR
+    for o in getattr(opt, "opts", (opt,)):
+        for name in ("lr_sched", "lr"):        # ShardedMasterSGD / MasterSGD, MultiTensorSGD32
+            s = getattr(o, name, None)
+            if isinstance(s, DeviceLR):
+                return s
+    return None
+
+
 def comm_name(opt) -> str:
     """How the optimizer moves gradients (for logs and the JSON line)."""
     from ..parallel.zero import ShardedMasterSGD
@@ -251,13 +343,20 @@ def comms_of(opt) -> list:
 
 
 def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None, loader=None,
-               loss_sum=None):
+               loss_sum=None, sched=None, host_lr=False):
     """One training step. ``head``: keyword arguments for ``ops.pool.cross_entropy``
     (``label_smoothing``, ``stats``, ``ignore_index``); None is the plain mean loss.
     ``loader``: a ``DeviceImageLoader`` whose ``next()`` opens the step (x and y are then its
     static buffers), so a captured step holds the input pipeline and every replay advances.
     ``loss_sum``: a device scalar the step adds its loss to (an epoch's mean without a host read
-    or a launch between replays)."""
+    or a launch between replays). ``sched``: a ``DeviceLR`` whose ``advance()`` opens the step
+    (one launch, captured with the rest); with ``host_lr`` it lives on the host and its value is
+    written into the optimizer's ``param_groups`` (the paths without a device learning rate)."""
+    if sched is not None:
+        sched.advance()
+        if host_lr:
+            for g in opt.param_groups:
+                g["lr"] = sched.value()
     s2d = False
     if loader is not None:
         x, y = loader.next()
@@ -287,7 +386,8 @@ def train_step(model, opt, x, y, amp_dtype, zero_grad=True, *, head=None, loader
     return loss.detach()
 
 
-def capture_step(model, opt, x, y, amp_dtype, *, head=None, loader=None, loss_sum=None):
+def capture_step(model, opt, x, y, amp_dtype, *, head=None, loader=None, loss_sum=None,
+                 sched=None):
     """The whole step as one hipGraph: ~800 kernels per ResNet-50 step replay without host
     launches or inter-kernel gaps. Gradients are None at capture, so the captured backward writes
     (not accumulates) them, and every replay reuses the same memory (static x, y)."""
@@ -295,7 +395,7 @@ def capture_step(model, opt, x, y, amp_dtype, *, head=None, loader=None, loss_su
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, capture_error_mode="thread_local"):
         loss = train_step(model, opt, x, y, amp_dtype, zero_grad=False, head=head, loader=loader,
-                          loss_sum=loss_sum)
+                          loss_sum=loss_sum, sched=sched)
     return g, loss
 
 
@@ -322,14 +422,8 @@ def main(argv=None) -> int:
     data = loader = None
     if has_data(args):
         data = open_data(args, dev, world, rank, "train")    # sets args.num_classes
-    model, opt, x, y = build(args, dev, world)
-    data_name = "synthetic"
     spe = 0                       # steps per epoch, the same on every rank
-    ep_loss, ep_steps = None, 0   # the running epoch's loss sum (device) and step count (host)
     if data is not None:
-        loader = make_loader(args, dev, rank, model, data, train=True)
-        x, y = loader.out, loader.labels_out
-        ep_loss = torch.zeros((), dtype=torch.float32, device=dev)
         meta = data[2]
         spe = (meta["n"] // world) // args.batch_size
         if spe < 1:
@@ -337,6 +431,23 @@ def main(argv=None) -> int:
                              f"{args.batch_size}")
         if args.num_epochs:
             args.num_batches = args.num_epochs * spe
+    segments = schedule_segments(
+        args, spe or IMAGENET_TRAIN_IMAGES / (args.batch_size * world), args.num_batches)
+    model, opt, x, y = build(args, dev, world, segments)
+    sched, host_lr = schedule_of(opt), False
+    if segments is not None and sched is None:
+        # no device learning rate on this path: the same schedule, evaluated on the host
+        from ..ops.schedule import DeviceLR
+        sched, host_lr = DeviceLR(segments, "cpu"), True
+        if rank == 0 and args.graph and dev.type == "cuda":
+            print("learning-rate schedule without master weights: the host sets lr every step, "
+                  "so the step runs eagerly (no hipGraph)", flush=True)
+    data_name = "synthetic"
+    ep_loss, ep_steps = None, 0   # the running epoch's loss sum (device) and step count (host)
+    if data is not None:
+        loader = make_loader(args, dev, rank, model, data, train=True)
+        x, y = loader.out, loader.labels_out
+        ep_loss = torch.zeros((), dtype=torch.float32, device=dev)
         data_name = f"{data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size})"
     head = stats = None
     if args.label_smoothing != 0.0 or args.print_training_accuracy:
@@ -356,21 +467,22 @@ def main(argv=None) -> int:
               f"{comm_name(opt)}", flush=True)
     for i in range(args.num_warmup_batches):
         t = time.perf_counter()
-        train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss)
+        train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss,
+                   sched=sched, host_lr=host_lr)
         sync()
         if rank == 0:   # the first steps include MIOpen's solver search: show progress
             print(f"warmup {i + 1}/{args.num_warmup_batches}: {time.perf_counter() - t:.2f} s",
                   flush=True)
     sync()
     graph = None
-    if args.graph and dev.type == "cuda":
+    if args.graph and dev.type == "cuda" and not host_lr:
         # Data parallel too: the bucket hooks fire during the captured backward, so the graph
         # holds the pack + collective (xGMI kernel on the comm stream, or RCCL) of every bucket
         # exactly where eager mode issues them; all ranks replay the same collective sequence.
         ok = True
         try:
             graph, g_loss = capture_step(model, opt, x, y, amp, head=head, loader=loader,
-                                         loss_sum=ep_loss)
+                                         loss_sum=ep_loss, sched=sched)
         except RuntimeError as e:  # capture refused by a library call: run eagerly
             graph, ok = None, False
             print(f"[rank {rank}] hipGraph capture failed, running eagerly: {e}", flush=True)
@@ -398,6 +510,8 @@ def main(argv=None) -> int:
         # reshuffle between replays needs no device read; the epoch's loss sum stays on the device
         loader.new_epoch()
         ep_loss.zero_()
+    if sched is not None:
+        sched.reset(0)   # the schedule counts the measured steps, as the epochs do
     t0 = t_last = time.perf_counter()
     loss = None
     for i in range(1, args.num_batches + 1):
@@ -409,7 +523,8 @@ def main(argv=None) -> int:
             graph.replay()
             loss = g_loss
         else:
-            loss = train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss)
+            loss = train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss,
+                              sched=sched, host_lr=host_lr)
         ep_steps += 1
         heartbeat.beat(i)
         if check is not None:
@@ -427,8 +542,9 @@ def main(argv=None) -> int:
                 seen = cur
             if rank == 0:
                 ips = n * args.batch_size / (now - t_last)
-                print(f"{i}\timages/sec: {ips:.1f} (per device)  loss {float(loss):.3f}{acc}",
-                      flush=True)
+                lr_col = f"  lr {sched.value():.6f}" if sched is not None else ""
+                print(f"{i}\timages/sec: {ips:.1f} (per device)  loss {float(loss):.3f}{acc}"
+                      f"{lr_col}", flush=True)
             t_last = now
     sync()
     elapsed = time.perf_counter() - t0
@@ -455,6 +571,9 @@ def main(argv=None) -> int:
                    "final_loss": round(float(loss), 4)}
             if counts is not None:
                 res.update(accuracy_fields(counts))
+            if sched is not None:
+                res.update({"final_lr": sched.value(),
+                            "lr_schedule": [list(s) for s in sched.segments]})
             if loader is not None:
                 res.update({"data": data[3], "images": data[2]["n"], "layout": loader.layout,
                             "steps_per_epoch": spe, "epochs": loader.epoch,

@@ -1,4 +1,5 @@
-"""ResNet v1.5 (bottleneck) in plain ``torch.nn`` -- the Horovod image's benchmark model family.
+"""ResNet v1.5 in plain ``torch.nn`` -- the Horovod image's benchmark model family (bottleneck
+ResNet-50/101/152; ResNet-18/34 of basic blocks, the small members tf_cnn_benchmarks also lists).
 
 The reference's allreduce demo runs the Horovod TF image's ``hvd-distribute.sh``
 (charts/tf-horovod/README.md:66-69, SURVEY §2.11 "Horovod TF image"). That image's benchmark is
@@ -41,6 +42,7 @@ def set_downsample_last(on: bool) -> None:
 
 DEPTHS = {"resnet50": [3, 4, 6, 3], "resnet101": [3, 4, 23, 3],
           "resnet152": [3, 8, 36, 3], "resnet_tiny": [1, 1, 1, 1]}
+BASIC_DEPTHS = {"resnet18": [2, 2, 2, 2], "resnet34": [3, 4, 6, 3]}
 
 
 class Bottleneck(nn.Module):
@@ -102,8 +104,40 @@ class Bottleneck(nn.Module):
                         link=link_out, res_out=rmask)
 
 
+class BasicBlock(nn.Module):
+    """conv3x3(stride)-BN-ReLU, conv3x3-BN, + shortcut, ReLU (ResNet-18/34). The same fused
+    pieces as :class:`Bottleneck` (conv-epilogue BN statistics, BN + residual add + ReLU in one
+    kernel pair), without its cross-layer backward hand-overs: autograd sums the block input's two
+    gradients and every BN reduces its own backward sums."""
+    expansion = 1
+
+    def __init__(self, cin: int, mid: int, stride: int):
+        super().__init__()
+        self.conv1 = Conv2dNHWC(cin, mid, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = BatchNormAct2d(mid, act="relu")
+        self.conv2 = Conv2dNHWC(mid, mid, 3, padding=1, bias=False)
+        self.bn2 = BatchNormAct2d(mid, act="relu")
+        nn.init.zeros_(self.bn2.weight)  # zero-init the residual branch's last BN
+        self.down_conv = self.down_bn = None
+        if stride != 1 or cin != mid:
+            self.down_conv = Conv2dNHWC(cin, mid, 1, stride=stride, bias=False)
+            self.down_bn = BatchNormAct2d(mid, act="none")
+
+    def forward(self, x, link: BNGradLink | None = None, link_out: BNGradLink | None = None):
+        """``link`` / ``link_out`` (see :class:`Bottleneck`) are accepted and left unused."""
+        y, st = self.conv1.forward_stats(x)
+        a = self.bn1(y, stats=st)
+        y, st = self.conv2.forward_stats(a)
+        idt = x
+        if self.down_conv is not None:
+            y_, st_ = self.down_conv.forward_stats(x)
+            idt = self.down_bn(y_, stats=st_)
+        return self.bn2(y, residual=idt, stats=st)
+
+
 class ResNet(nn.Module):
-    def __init__(self, depths: List[int], num_classes: int = 1000, width: int = 64):
+    def __init__(self, depths: List[int], num_classes: int = 1000, width: int = 64,
+                 block=Bottleneck):
         super().__init__()
         self.stem = nn.Sequential(StemConv2d(3, width, 7, stride=2, padding=3, bias=False),
                                   BatchNormAct2d(width, act="relu"),
@@ -113,8 +147,8 @@ class ResNet(nn.Module):
         for i, n in enumerate(depths):
             mid = width * (2 ** i)
             for j in range(n):
-                layers.append(Bottleneck(cin, mid, stride=2 if (j == 0 and i > 0) else 1))
-                cin = mid * Bottleneck.expansion
+                layers.append(block(cin, mid, stride=2 if (j == 0 and i > 0) else 1))
+                cin = mid * block.expansion
         self.layers = nn.Sequential(*layers)
         self.fc = nn.Linear(cin, num_classes)
         for m in self.modules():
@@ -145,8 +179,10 @@ class ResNet(nn.Module):
 
 
 def resnet(name: str = "resnet50", num_classes: int = 1000, width: int = 64) -> ResNet:
+    if name in BASIC_DEPTHS:
+        return ResNet(BASIC_DEPTHS[name], num_classes=num_classes, width=width, block=BasicBlock)
     depths = DEPTHS.get(name)
     if depths is None:
         raise ValueError(f"unknown model {name!r}; choose one of "
-                         f"{sorted(DEPTHS)}")
+                         f"{sorted(list(DEPTHS) + list(BASIC_DEPTHS))}")
     return ResNet(depths, num_classes=num_classes, width=width)

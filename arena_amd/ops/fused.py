@@ -137,18 +137,47 @@ def unflatten_from(tensors: Sequence[Tensor], offsets: Sequence[int], flat: Tens
     _impl(flat).mt_copy_scale(list(tensors), [int(o) for o in offsets], flat, float(scale), 1)
 
 
+def _check_lr_t(lr_t: Optional[Tensor], like: Tensor) -> Optional[Tensor]:
+    """A device learning rate is one fp32 value on the updated tensors' device."""
+    if lr_t is not None and (lr_t.dtype != torch.float32 or lr_t.numel() != 1
+                             or lr_t.device != like.device):
+        raise ValueError(f"lr_t must be a float32 [1] tensor on {like.device} (got {lr_t.dtype} "
+                         f"{tuple(lr_t.shape)} on {lr_t.device})")
+    return lr_t
+
+
 def mt_sgd_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tensor, mom: Tensor,
-                  wbf: Tensor, *, lr: float, momentum: float, weight_decay: float) -> None:
+                  wbf: Tensor, *, lr: float, momentum: float, weight_decay: float,
+                  lr_t: Optional[Tensor] = None) -> None:
     """One launch (per 48 tensors) of momentum SGD over bf16 grads with fp32 master weights;
-    also writes the rounded bf16 weights into ``wbf`` (see ``mt_sgd_master_kernel``)."""
+    also writes the rounded bf16 weights into ``wbf`` (see ``mt_sgd_master_kernel``). ``lr_t``
+    (optional, fp32 [1]) is read by the kernel instead of ``lr``: a schedule under graph replay."""
     _impl(master).mt_sgd_master(list(grads), [int(o) for o in offsets], master, mom, wbf,
-                                float(lr), float(momentum), float(weight_decay))
+                                float(lr), float(momentum), float(weight_decay),
+                                lr_t=_check_lr_t(lr_t, master))
+
+
+def mt_sgd_f32(grads: Sequence[Tensor], offsets: Sequence[int], w: Tensor, mom: Tensor, *,
+               lr: float, momentum: float, weight_decay: float = 0.0, scale: float = 1.0,
+               lr_t: Optional[Tensor] = None) -> None:
+    """Momentum SGD over fp32 tensors (BN scales/shifts, biases), one launch per 48 tensors:
+    gradient i updates ``w`` / ``mom`` at ``[offsets[i], offsets[i] + numel_i)`` in place, any
+    sizes; d = g * scale + wd * w; mom = momentum * mom + d; w -= lr * mom."""
+    _impl(w).mt_sgd_f32(list(grads), [int(o) for o in offsets], w, mom, float(lr), float(momentum),
+                        float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w))
 
 
 def shard_sgd(grad: Tensor, w32: Tensor, mom: Tensor, wbf: Optional[Tensor] = None, *, lr: float,
-              momentum: float, weight_decay: float, scale: float) -> None:
+              momentum: float, weight_decay: float, scale: float,
+              lr_t: Optional[Tensor] = None) -> None:
     """Momentum SGD over one flat range (a rank's shard of a reduce-scattered bucket):
     d = grad * scale + wd * w32; mom = momentum * mom + d; w32 -= lr * mom; with bf16 ``grad``
     the fp32 ``w32`` are masters and ``wbf`` receives the rounded bf16 weights."""
     _impl(w32).shard_sgd(grad, w32, mom, wbf, float(lr), float(momentum), float(weight_decay),
-                         float(scale))
+                         float(scale), lr_t=_check_lr_t(lr_t, w32))
+
+
+def lr_schedule(table: Tensor, step: Tensor, lr: Tensor) -> None:
+    """``lr[0] = schedule(step[0])``, then ``step[0] += 1``, in one launch (``table``: the segment
+    table of :func:`arena_amd.ops.schedule.encode`)."""
+    _impl(lr).lr_schedule(table, step, lr)

@@ -275,7 +275,12 @@ def _storage_flat(t):
     return t.as_strided((t.numel(),), (1,), t.storage_offset())
 
 
-def mt_sgd_master(grads, offsets, master, mom, wbf, lr, momentum, weight_decay):
+def _lr_value(lr, lr_t):
+    return float(lr_t.reshape(-1)[0].item()) if lr_t is not None else lr
+
+
+def mt_sgd_master(grads, offsets, master, mom, wbf, lr, momentum, weight_decay, lr_t=None):
+    lr = _lr_value(lr, lr_t)
     for g, off in zip(grads, offsets):
         n = g.numel()
         w, m = master[off:off + n], mom[off:off + n]
@@ -284,8 +289,29 @@ def mt_sgd_master(grads, offsets, master, mom, wbf, lr, momentum, weight_decay):
         wbf[off:off + n].copy_(w)
 
 
-def shard_sgd(grad, w32, mom, wbf, lr, momentum, weight_decay, scale):
+def mt_sgd_f32(grads, offsets, w, mom, lr, momentum, weight_decay, scale, lr_t=None):
+    """CPU reference of the HIP ``mt_sgd_f32`` kernel (same operation order as ``shard_sgd``)."""
+    lr = _lr_value(lr, lr_t)
+    for g, off in zip(grads, offsets):
+        n = g.numel()
+        ws, m = w[off:off + n], mom[off:off + n]
+        d = _storage_flat(g) * scale + weight_decay * ws
+        m.mul_(momentum).add_(d)
+        ws.sub_(lr * m)
+
+
+def lr_schedule(table, step, lr):
+    """CPU form of the ``arena_lr_schedule`` kernel: decodes the device table and evaluates
+    :func:`arena_amd.ops.schedule.reference_lr`."""
+    from . import schedule
+    t = int(step.reshape(-1)[0].item())
+    lr.fill_(float(schedule.reference_lr(schedule.decode(table), t)))
+    step.add_(1)
+
+
+def shard_sgd(grad, w32, mom, wbf, lr, momentum, weight_decay, scale, lr_t=None):
     """CPU reference of the HIP ``shard_sgd`` kernel (same operation order)."""
+    lr = _lr_value(lr, lr_t)
     d = grad.float() * scale + weight_decay * w32
     mom.mul_(momentum).add_(d)
     w32.sub_(lr * mom)

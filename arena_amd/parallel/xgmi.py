@@ -404,7 +404,8 @@ class XgmiComm:
         wbf[off:off + n].copy_(w0.to(bf))
         ref_w, ref_m = w0.clone(), torch.zeros(n, device="cuda")
         lr, mu, wd = 2.0 ** -4, 0.5, 2.0 ** -10
-        for step in range(2):
+        lr_t = torch.full((1,), lr, device="cuda")
+        for step in range(3):                            # the last one in the lr_ptr form
             g = self._grad_rows(n, step, 0.25)
             stage[off:off + n].copy_(g[self.rank].to(bf))
             gsum = g[0].clone()
@@ -414,7 +415,10 @@ class XgmiComm:
             ref_w = ref_w - lr * ref_m
             self._prewarm()
             self._gate()
-            self.peers.sgd_bf16(master, mom, off, n, lr, mu, wd, 1.0)
+            if step < 2:
+                self.peers.sgd_bf16(master, mom, off, n, lr, mu, wd, 1.0)
+            else:   # a kernel that ignored lr_ptr would step with lr 0 and mismatch
+                self.peers.sgd_bf16(master, mom, off, n, 0.0, mu, wd, 1.0, lr_t)
             torch.cuda.synchronize()
             if not torch.equal(wbf[off:off + n], ref_w.to(bf)):
                 return False
@@ -432,7 +436,8 @@ class XgmiComm:
         mom = torch.zeros(n, device="cuda")
         ref_w, ref_m = w0.clone(), torch.zeros(n, device="cuda")
         lr, mu, wd = 2.0 ** -4, 0.5, 2.0 ** -10
-        for step in range(2):
+        lr_t = torch.full((1,), lr, device="cuda")
+        for step in range(3):                            # the last one in the lr_ptr form
             g = self._grad_rows(n, step, 0.25)
             self._buf[off:off + n].copy_(g[self.rank])
             gsum = g[0].clone()
@@ -442,7 +447,10 @@ class XgmiComm:
             ref_w = ref_w - lr * ref_m
             self._prewarm()
             self._gate()
-            self.peers.sgd_f32(mom, off, n, lr, mu, wd, 1.0)
+            if step < 2:
+                self.peers.sgd_f32(mom, off, n, lr, mu, wd, 1.0)
+            else:
+                self.peers.sgd_f32(mom, off, n, 0.0, mu, wd, 1.0, lr_t)
             torch.cuda.synchronize()
             if not torch.equal(self._buf2[off:off + n], ref_w):
                 return False

@@ -52,8 +52,15 @@ arrived (unused parameters: zero gradient, as Horovod) and joins the comm stream
   raises instead of silently dropping its gradients;
 * to be able to skip a step after seeing the loss (non-finite loss, warmup), construct with
   ``overlap=False``: hooks only record readiness and ``step()`` launches every bucket;
-* hyperparameters are read from ``param_groups`` at launch time (an lr schedule works eagerly;
-  a captured hipGraph bakes the values in at capture).
+* hyperparameters are read from ``param_groups`` at launch time. A float ``lr`` is a kernel
+  argument, which a captured hipGraph keeps as it was at capture; pass a
+  :class:`arena_amd.ops.schedule.DeviceLR` as ``lr`` instead and every update kernel (xGMI, RCCL
+  and hier alike) reads the learning rate from its device value, so a schedule moves on under
+  graph replay. Every rank owns its ``DeviceLR`` and advances it on its main stream at the head
+  of the step, before the backward: each bucket's update is launched on the comm stream after
+  ``stream.wait_stream(main)`` from a hook of that backward, hence after the advance, and the
+  next step's advance follows the join of the comm stream at ``step()``. All ranks evaluate the
+  same schedule at the same step, so the replicas stay bit-identical.
 
 Masters and momentum are full-length arrays of which each rank updates only the chunks it
 owns; :meth:`state_dict` reassembles them.
@@ -68,6 +75,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops.optim import _same_memory_order
+from ..ops.schedule import DeviceLR, attach_state, restore_state
 from ..runtime import heartbeat
 
 Tensor = torch.Tensor
@@ -114,9 +122,12 @@ class ShardedMasterSGD:
     bf16 weights with fp32 masters (the parameters are converted in place), or fp32 weights that
     are their own masters. Parameters must be contiguous or channels_last; CUDA tensors (CPU
     tensors with ``backend="rccl"`` over gloo, for tests). ``order``: the parameters in model
-    (registration) order, which decides the buckets (default: the param groups' order)."""
+    (registration) order, which decides the buckets (default: the param groups' order).
+    ``lr``: a float, or a :class:`DeviceLR` on the parameters' device that the caller advances at
+    the head of every step (see "Update timing" above); a group's own ``lr`` override stays a
+    float, groups without one read the device value."""
 
-    def __init__(self, params: Iterable, lr: float, momentum: float = 0.0,
+    def __init__(self, params: Iterable, lr, momentum: float = 0.0,
                  weight_decay: float = 0.0, bucket_mb: float = 16.0, group=None,
                  timeout_s: float = 60.0, overlap: bool = True, backend: str = "auto",
                  order: Optional[Iterable[Tensor]] = None, last_bucket_mb: Optional[float] = None,
@@ -127,9 +138,16 @@ class ShardedMasterSGD:
         else:
             raw_groups = [{"params": plist}]
         self.param_groups = []
+        self.lr_sched: Optional[DeviceLR] = lr if isinstance(lr, DeviceLR) else None
+        self._sched_groups = set()      # indices of the groups that follow the DeviceLR
         for g in raw_groups:
             ps = [p for p in g["params"]]
-            self.param_groups.append({"params": ps, "lr": float(g.get("lr", lr)),
+            if self.lr_sched is not None and "lr" not in g:
+                self._sched_groups.add(len(self.param_groups))
+                lr_g = float(self.lr_sched.lr.item())      # informational; the kernels read lr_t
+            else:
+                lr_g = float(g.get("lr", lr))
+            self.param_groups.append({"params": ps, "lr": lr_g,
                                       "momentum": float(g.get("momentum", momentum)),
                                       "weight_decay": float(g.get("weight_decay", weight_decay))})
         self.params: List[Tensor] = [p for g in self.param_groups for p in g["params"]]
@@ -148,6 +166,9 @@ class ShardedMasterSGD:
         self.rank = dist.get_rank(group)
         dev = self.params[0].device
         self.device = dev
+        if self.lr_sched is not None and self.lr_sched.device != dev:
+            raise ValueError(f"the DeviceLR lives on {self.lr_sched.device}, the parameters on "
+                             f"{dev}")
         kind_of = {}
         for gi, g in enumerate(self.param_groups):
             kind = {"bf16": _BF16, "fp32": _F32}.get(raw_groups[gi].get("weights", "bf16"))
@@ -392,21 +413,22 @@ class ShardedMasterSGD:
             for r in b.ranges:
                 g = self.param_groups[r.gi]
                 lr, mu, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
+                lr_t = self.lr_sched.lr if r.gi in self._sched_groups else None
                 if self.comm is not None:
-                    self._update_xgmi(r, lr, mu, wd)
+                    self._update_xgmi(r, lr, mu, wd, lr_t)
                 else:
-                    self._update_rccl(r, lr, mu, wd)
+                    self._update_rccl(r, lr, mu, wd, lr_t)
         b.launched = True
 
-    def _update_xgmi(self, r: _Range, lr, mu, wd) -> None:
+    def _update_xgmi(self, r: _Range, lr, mu, wd, lr_t=None) -> None:
         if r.dtype == _BF16:
             self.comm.peers.sgd_bf16(self.master, self.mom, r.start, r.end - r.start, lr, mu, wd,
-                                     1.0 / self.world)
+                                     1.0 / self.world, lr_t)
         else:
             self.comm.peers.sgd_f32(self.mom32[r.start:r.end], self.f0 + r.start,
-                                    r.end - r.start, lr, mu, wd, 1.0 / self.world)
+                                    r.end - r.start, lr, mu, wd, 1.0 / self.world, lr_t)
 
-    def _update_rccl(self, r: _Range, lr, mu, wd) -> None:
+    def _update_rccl(self, r: _Range, lr, mu, wd, lr_t=None) -> None:
         """reduce-scatter -> shard_sgd on the owned shard -> all-gather, on the current (comm)
         stream. Sub-ranges are padded to world x 16-byte slots: equal, aligned shards. The
         hierarchical backend does each collective in two levels (node, then between nodes)."""
@@ -426,13 +448,13 @@ class ShardedMasterSGD:
                 self._reduce_scatter(out, self.stage[r.start:r.end])
             fused.shard_sgd(out, self.master[lo:lo + sl], self.mom[lo:lo + sl],
                             self.wbf[lo:lo + sl], lr=lr, momentum=mu, weight_decay=wd,
-                            scale=scale)
+                            scale=scale, lr_t=lr_t)
             self._all_gather(self.wbf, r.start, n, lo, sl)
         else:
             out = self._rs_out[:sl]
             self._reduce_scatter(out, self.stage32[r.start:r.end])
             fused.shard_sgd(out, self.w32[lo:lo + sl], self.mom32[lo:lo + sl], None, lr=lr,
-                            momentum=mu, weight_decay=wd, scale=scale)
+                            momentum=mu, weight_decay=wd, scale=scale, lr_t=lr_t)
             self._all_gather(self.w32, r.start, n, lo, sl)
 
     def _reduce_scatter(self, out: Tensor, inp: Tensor) -> None:
@@ -587,10 +609,11 @@ class ShardedMasterSGD:
             else:
                 masters.append(self._logical(self.w32, p).clone())
                 moms.append(self._logical(mom32, p))
-        return {"master": masters, "momentum_buffer": moms,
-                "shapes": [tuple(p.shape) for p in self.params],
-                "param_groups": [{k: v for k, v in g.items() if k != "params"}
-                                 for g in self.param_groups]}
+        state = {"master": masters, "momentum_buffer": moms,
+                 "shapes": [tuple(p.shape) for p in self.params],
+                 "param_groups": [{k: v for k, v in g.items() if k != "params"}
+                                  for g in self.param_groups]}
+        return attach_state(state, self.lr_sched)
 
     @torch.no_grad()
     def load_state_dict(self, state: dict) -> None:
@@ -623,6 +646,7 @@ class ShardedMasterSGD:
             for k in ("lr", "momentum", "weight_decay"):
                 if k in st:
                     g[k] = float(st[k])
+        restore_state(state, self.lr_sched)
         self._rebind()
 
     @torch.no_grad()

@@ -494,7 +494,8 @@ __global__ __launch_bounds__(kThreads) void xgmi_sgd_bf16_kernel(ArenaXgmiPeers 
                                                                   float* __restrict__ mom,
                                                                   long long off, long long n,
                                                                   long long L, long long S,
-                                                                  SgdCoef c) {
+                                                                  SgdCoef c, const float* lr_ptr) {
+  if (lr_ptr) c.lr = *lr_ptr;  // device learning rate (schedules under graph replay)
   const int b = blockIdx.x;
   const uint32_t e = P.epoch[b] + 1;
   const long long lo = (long long)b * S;
@@ -582,7 +583,8 @@ __global__ __launch_bounds__(kThreads) void xgmi_sgd_f32_kernel(ArenaXgmiPeers P
                                                                  float* __restrict__ mom,
                                                                  long long off, long long n,
                                                                  long long L, long long S,
-                                                                 SgdCoef c) {
+                                                                 SgdCoef c, const float* lr_ptr) {
+  if (lr_ptr) c.lr = *lr_ptr;
   const int b = blockIdx.x;
   const uint32_t e = P.epoch[b] + 1;
   const long long lo = (long long)b * S;
@@ -797,8 +799,8 @@ void sgd_geometry(long long n, int W, long long* L, long long* S, int* nb) {
 // One bucket [off, off + n) (bf16 elements, off and n multiples of 8) of the sharded SGD: bf16
 // grads staged in every rank's buf, bf16 weights in every rank's buf2, fp32 master/mom local.
 hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom, long long off,
-                              long long n, float lr, float momentum, float wd, float scale,
-                              hipStream_t stream) {
+                              long long n, float lr, const float* lr_ptr, float momentum, float wd,
+                              float scale, hipStream_t stream) {
   const int W = P->world;
   if (W < 2 || W > kMaxR || n <= 0 || off < 0 || n % 8 || off % 8 || P->buf2[0] == nullptr)
     return hipErrorInvalidValue;
@@ -809,7 +811,7 @@ hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom
   sgd_geometry(n, W, &L, &S, &nb);
   SgdCoef c{lr, momentum, wd, scale};
   ARENA_CCL_DISPATCH(W, xgmi_sgd_bf16_kernel, dim3(nb), dim3(kThreads), 0, stream, *P, master, mom,
-                     off, n, L, S, c);
+                     off, n, L, S, c, lr_ptr);
   return hipGetLastError();
 }
 
@@ -826,7 +828,8 @@ void arena_ccl_sgd_shard(long long off, long long n, int world, int r, long long
 // One fp32 bucket [off, off + n) (floats, multiples of 4) of the sharded SGD: fp32 grads staged in
 // every rank's buf, fp32 weights (= masters) in every rank's buf2, momentum local (bucket-relative).
 hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off, long long n,
-                             float lr, float momentum, float wd, float scale, hipStream_t stream) {
+                             float lr, const float* lr_ptr, float momentum, float wd, float scale,
+                             hipStream_t stream) {
   const int W = P->world;
   if (W < 2 || W > kMaxR || n <= 0 || off < 0 || n % 4 || off % 4 || P->buf2[0] == nullptr)
     return hipErrorInvalidValue;
@@ -836,7 +839,7 @@ hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off,
   geometry(n, W, &L, &S, &nb);
   SgdCoef c{lr, momentum, wd, scale};
   ARENA_CCL_DISPATCH(W, xgmi_sgd_f32_kernel, dim3(nb), dim3(kThreads), 0, stream, *P, mom, off, n,
-                     L, S, c);
+                     L, S, c, lr_ptr);
   return hipGetLastError();
 }
 

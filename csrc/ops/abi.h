@@ -231,11 +231,19 @@ hipError_t arena_softmax_xent(const float* logits, const long long* labels, int 
 hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const long long* ns,
                                int count, float* flat, float scale, int dir, hipStream_t stream);
 hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, const long long* ns,
-                               int count, float* master, float* mom, void* wbf, float lr, float mu,
-                               float wd, hipStream_t stream);
+                               int count, float* master, float* mom, void* wbf, float lr,
+                               const float* lr_ptr, float mu, float wd, hipStream_t stream);
 hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
-                           long long n, float lr, float mu, float wd, float scale,
-                           hipStream_t stream);
+                           long long n, float lr, const float* lr_ptr, float mu, float wd,
+                           float scale, hipStream_t stream);
+// fp32 multi-tensor momentum SGD: gradient i updates w/mom[offs[i], offs[i] + ns[i]) (any sizes).
+hipError_t arena_mt_sgd_f32(const float* const* grads, const long long* offs, const long long* ns,
+                            int count, float* w, float* mom, float lr, const float* lr_ptr,
+                            float mu, float wd, float scale, hipStream_t stream);
+// lr[0] = value of the piecewise-linear schedule seg[n_seg][4] (begin, end, lr0 bits, lr1 bits;
+// fp64 values as int64 bit patterns) at *step, then *step += 1.
+hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
+                             hipStream_t stream);
 #ifdef ARENA_TIMELINE
 hipError_t arena_timeline_read(long long* host, int clear);
 #endif
@@ -353,12 +361,13 @@ hipError_t arena_ccl_broadcast(const ArenaXgmiPeers* P, const float* in, float* 
                                int root, hipStream_t stream);
 void arena_ccl_set_bcast_direct_max(long long e);
 hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom, long long off,
-                              long long n, float lr, float momentum, float wd, float scale,
-                              hipStream_t stream);
+                              long long n, float lr, const float* lr_ptr, float momentum, float wd,
+                              float scale, hipStream_t stream);
 void arena_ccl_sgd_shard(long long off, long long n, int world, int r, long long* lo,
                          long long* hi);
 hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off, long long n,
-                             float lr, float momentum, float wd, float scale, hipStream_t stream);
+                             float lr, const float* lr_ptr, float momentum, float wd, float scale,
+                             hipStream_t stream);
 void arena_ccl_sgd_f32_shard(long long off, long long n, int world, int r, long long* lo,
                              long long* hi);
 hipError_t arena_ccl_allgather(const ArenaXgmiPeers* P, const float* in, float* out, long long m,

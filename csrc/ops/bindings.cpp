@@ -41,6 +41,15 @@ const long long* opt_i64_scalar(const OptT& t, const char* name) {
   return reinterpret_cast<const long long*>(t->data_ptr<int64_t>());
 }
 
+// Optional device learning rate (a schedule's value under graph replay): fp32 [1] on `like`'s GPU.
+const float* opt_lr_ptr(const OptT& lr_t, const Tensor& like, const char* what) {
+  if (!lr_t.has_value()) return nullptr;
+  check_f32(*lr_t, "lr_t");
+  TORCH_CHECK(lr_t->numel() == 1, what, ": lr_t must hold one float32 value");
+  TORCH_CHECK(lr_t->device() == like.device(), what, ": lr_t must be on the updated tensors' GPU");
+  return lr_t->data_ptr<float>();
+}
+
 int dtype_code(const Tensor& t) {
   switch (t.scalar_type()) {
     case torch::kFloat32: return 0;
@@ -495,8 +504,10 @@ void mt_copy_scale(std::vector<Tensor> tensors, std::vector<int64_t> offsets, Te
 }
 
 void mt_sgd_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
-                   Tensor mom, Tensor wbf, double lr, double momentum, double weight_decay) {
+                   Tensor mom, Tensor wbf, double lr, double momentum, double weight_decay,
+                   OptT lr_t) {
   check_f32(master, "master");
+  const float* lp = opt_lr_ptr(lr_t, master, "mt_sgd_master");
   check_f32(mom, "mom");
   check_dev(wbf, "wbf");
   TORCH_CHECK(wbf.scalar_type() == torch::kBFloat16 && wbf.is_contiguous() &&
@@ -521,13 +532,66 @@ void mt_sgd_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tens
   }
   check_hip(arena_mt_sgd_master(ptrs.data(), offs.data(), ns.data(), (int)ptrs.size(),
                                 master.data_ptr<float>(), mom.data_ptr<float>(), wbf.data_ptr(),
-                                (float)lr, (float)momentum, (float)weight_decay, cur_stream()),
+                                (float)lr, lp, (float)momentum, (float)weight_decay,
+                                cur_stream()),
             "mt_sgd_master");
 }
 
+// Momentum SGD on fp32 tensors: gradient i updates w/mom[offsets[i], offsets[i] + numel_i).
+void mt_sgd_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor mom,
+                double lr, double momentum, double weight_decay, double scale, OptT lr_t) {
+  check_f32(w, "w");
+  check_f32(mom, "mom");
+  const float* lp = opt_lr_ptr(lr_t, w, "mt_sgd_f32");
+  TORCH_CHECK(mom.numel() == w.numel() && mom.device() == w.device(),
+              "mt_sgd_f32: w and mom must be equal-size buffers on one GPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(mom.data_ptr()) % 16 == 0,
+              "mt_sgd_f32: w and mom must be 16-byte aligned");
+  TORCH_CHECK(grads.size() == offsets.size(), "offsets length");
+  std::vector<const float*> ptrs;
+  std::vector<long long> offs, ns;
+  for (size_t i = 0; i < grads.size(); ++i) {
+    const Tensor& g = grads[i];
+    TORCH_CHECK(g.is_cuda() && g.device() == w.device(), "grad ", i, " must be on w's GPU");
+    TORCH_CHECK(g.scalar_type() == torch::kFloat32 && g.is_non_overlapping_and_dense(),
+                "mt_sgd_f32: grad ", i, " must be dense fp32");
+    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + g.numel() <= w.numel(), "mt_sgd_f32: segment ", i,
+                " out of bounds");
+    ptrs.push_back(g.data_ptr<float>());
+    offs.push_back(offsets[i]);
+    ns.push_back(g.numel());
+  }
+  check_hip(arena_mt_sgd_f32(ptrs.data(), offs.data(), ns.data(), (int)ptrs.size(),
+                             w.data_ptr<float>(), mom.data_ptr<float>(), (float)lr, lp,
+                             (float)momentum, (float)weight_decay, (float)scale, cur_stream()),
+            "mt_sgd_f32");
+}
+
+// lr[0] = schedule(seg)(step[0]); step[0] += 1. seg: int64 [n, 4] rows (begin, end, lr0, lr1) with
+// the fp64 values as bit patterns (arena_amd/ops/schedule.py).
+void lr_schedule(Tensor seg, Tensor step, Tensor lr) {
+  check_dev(seg, "seg");
+  check_dev(step, "step");
+  check_f32(lr, "lr");
+  TORCH_CHECK(seg.scalar_type() == torch::kInt64 && seg.dim() == 2 && seg.size(1) == 4 &&
+                  seg.size(0) >= 1 && seg.size(0) <= 64,
+              "lr_schedule: seg must be int64 [n, 4] with 1 <= n <= 64");
+  TORCH_CHECK(step.scalar_type() == torch::kInt64 && step.numel() == 1 && lr.numel() == 1,
+              "lr_schedule: step must be int64 [1] and lr float32 [1]");
+  TORCH_CHECK(seg.device() == lr.device() && step.device() == lr.device(),
+              "lr_schedule: seg, step and lr must share one GPU");
+  check_hip(arena_lr_schedule(reinterpret_cast<const long long*>(seg.data_ptr<int64_t>()),
+                              (int)seg.size(0),
+                              reinterpret_cast<long long*>(step.data_ptr<int64_t>()),
+                              lr.data_ptr<float>(), cur_stream()),
+            "lr_schedule");
+}
+
 void shard_sgd(Tensor grad, Tensor w32, Tensor mom, c10::optional<Tensor> wbf, double lr,
-               double momentum, double weight_decay, double scale) {
+               double momentum, double weight_decay, double scale, OptT lr_t) {
   check_f32(w32, "w32");
+  const float* lp = opt_lr_ptr(lr_t, w32, "shard_sgd");
   check_f32(mom, "mom");
   check_dev(grad, "grad");
   const bool bf = grad.scalar_type() == torch::kBFloat16;
@@ -554,7 +618,7 @@ void shard_sgd(Tensor grad, Tensor w32, Tensor mom, c10::optional<Tensor> wbf, d
     TORCH_CHECK(!wbf.has_value(), "shard_sgd: fp32 weights are their own masters (no wbf)");
   }
   check_hip(arena_shard_sgd(grad.data_ptr(), bf ? 1 : 0, w32.data_ptr<float>(),
-                            mom.data_ptr<float>(), wp, n, (float)lr, (float)momentum,
+                            mom.data_ptr<float>(), wp, n, (float)lr, lp, (float)momentum,
                             (float)weight_decay, (float)scale, cur_stream()),
             "shard_sgd");
 }
@@ -1862,8 +1926,9 @@ class XgmiPeers {
 
   // Sharded momentum SGD over one bucket [off, off + n) of bf16 elements (see xgmi_ccl.hip).
   void sgd_bf16(Tensor master, Tensor mom, int64_t off, int64_t n, double lr, double momentum,
-                double wd, double scale) {
+                double wd, double scale, OptT lr_t) {
     check_f32(master, "master");
+    const float* lp = opt_lr_ptr(lr_t, master, "sgd_bf16");
     check_f32(mom, "mom");
     TORCH_CHECK(p_.buf2[0] != nullptr, "sgd_bf16 needs the weight buffers (buf2)");
     TORCH_CHECK(off >= 0 && n > 0 && off % 8 == 0 && n % 8 == 0, "sgd_bf16: off/n must be "
@@ -1873,22 +1938,24 @@ class XgmiPeers {
     TORCH_CHECK((off + n + 1) / 2 <= p_.buf_elems && (off + n + 1) / 2 <= p_.buf2_elems,
                 "sgd_bf16: bucket exceeds the registered buffers");
     check_hip(arena_ccl_sgd_bf16(&p_, master.data_ptr<float>(), mom.data_ptr<float>(), off, n,
-                                 (float)lr, (float)momentum, (float)wd, (float)scale, cur_stream()),
+                                 (float)lr, lp, (float)momentum, (float)wd, (float)scale,
+                                 cur_stream()),
               "xgmi_sgd_bf16");
   }
 
   // The fp32 tail bucket [off, off + n) (floats) of the same optimizer; `mom` holds the bucket's
   // momentum (bucket-relative, n floats).
   void sgd_f32(Tensor mom, int64_t off, int64_t n, double lr, double momentum, double wd,
-               double scale) {
+               double scale, OptT lr_t) {
     check_f32(mom, "mom");
+    const float* lp = opt_lr_ptr(lr_t, mom, "sgd_f32");
     TORCH_CHECK(p_.buf2[0] != nullptr, "sgd_f32 needs the weight buffers (buf2)");
     TORCH_CHECK(off >= 0 && n > 0 && off % 4 == 0 && n % 4 == 0, "sgd_f32: off/n must be "
                 "multiples of 4");
     TORCH_CHECK(mom.numel() >= n, "sgd_f32: mom too short");
     TORCH_CHECK(off + n <= p_.buf_elems && off + n <= p_.buf2_elems,
                 "sgd_f32: bucket exceeds the registered buffers");
-    check_hip(arena_ccl_sgd_f32(&p_, mom.data_ptr<float>(), off, n, (float)lr, (float)momentum,
+    check_hip(arena_ccl_sgd_f32(&p_, mom.data_ptr<float>(), off, n, (float)lr, lp, (float)momentum,
                                 (float)wd, (float)scale, cur_stream()),
               "xgmi_sgd_f32");
   }
@@ -2001,10 +2068,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sgd_flat", &sgd_flat);
   m.def("softmax_xent", &softmax_xent);
   m.def("mt_copy_scale", &mt_copy_scale);
-  m.def("mt_sgd_master", &mt_sgd_master);
+  m.def("mt_sgd_master", &mt_sgd_master, py::arg("grads"), py::arg("offsets"), py::arg("master"),
+        py::arg("mom"), py::arg("wbf"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("lr_t") = py::none());
+  m.def("mt_sgd_f32", &mt_sgd_f32, py::arg("grads"), py::arg("offsets"), py::arg("w"),
+        py::arg("mom"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("scale"), py::arg("lr_t") = py::none());
+  m.def("lr_schedule", &lr_schedule);
   m.def("shard_sgd", &shard_sgd, py::arg("grad"), py::arg("w32"), py::arg("mom"),
         py::arg("wbf") = py::none(), py::arg("lr"), py::arg("momentum"),
-        py::arg("weight_decay"), py::arg("scale"));
+        py::arg("weight_decay"), py::arg("scale"), py::arg("lr_t") = py::none());
   m.def("ccl_malloc", &ccl_malloc);
   m.def("ccl_free", &ccl_free);
   m.def("ccl_memset", &ccl_memset);
@@ -2038,8 +2111,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("adam", &XgmiPeers::adam)
       .def("broadcast", &XgmiPeers::broadcast)
       .def("allgather", &XgmiPeers::allgather)
-      .def("sgd_bf16", &XgmiPeers::sgd_bf16)
-      .def("sgd_f32", &XgmiPeers::sgd_f32)
+      .def("sgd_bf16", &XgmiPeers::sgd_bf16, py::arg("master"), py::arg("mom"), py::arg("off"),
+           py::arg("n"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("scale"),
+           py::arg("lr_t") = py::none())
+      .def("sgd_f32", &XgmiPeers::sgd_f32, py::arg("mom"), py::arg("off"), py::arg("n"),
+           py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("scale"),
+           py::arg("lr_t") = py::none())
       .def_property_readonly("world", &XgmiPeers::world)
       .def_property("push", &XgmiPeers::push, &XgmiPeers::set_push);
 #ifdef ARENA_TIMELINE

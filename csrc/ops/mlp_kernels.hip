@@ -1159,7 +1159,9 @@ __device__ inline uint32_t f32_to_bf16(float f) {
 __global__ __launch_bounds__(256) void mt_sgd_master_kernel(MtArgs a, float* __restrict__ master,
                                                             float* __restrict__ mom,
                                                             uint16_t* __restrict__ wbf, float lr,
-                                                            float mu, float wd) {
+                                                            const float* lr_ptr, float mu,
+                                                            float wd) {
+  if (lr_ptr) lr = *lr_ptr;  // device learning rate (schedules under graph replay)
   int ti = 0;
   for (int i = 1; i < a.count; ++i)
     if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
@@ -1196,8 +1198,9 @@ __global__ __launch_bounds__(256) void shard_sgd_kernel(const void* __restrict__
                                                         float* __restrict__ w32,
                                                         float* __restrict__ mom,
                                                         uint16_t* __restrict__ wbf, long long n,
-                                                        float lr, float mu, float wd,
-                                                        float scale) {
+                                                        float lr, const float* lr_ptr, float mu,
+                                                        float wd, float scale) {
+  if (lr_ptr) lr = *lr_ptr;
   const long long stride = (long long)gridDim.x * 1024;
   for (long long j = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; j < n; j += stride) {
     float g[4];
@@ -1231,6 +1234,87 @@ __global__ __launch_bounds__(256) void shard_sgd_kernel(const void* __restrict__
                                                       f32_to_bf16(w[2]) | (f32_to_bf16(w[3]) << 16));
     }
   }
+}
+
+// Momentum SGD over fp32 tensors with fp32 gradients (BatchNorm scales/shifts, biases), same
+// MtArgs walk as mt_sgd_master: gradient at a.ptr[i], weight/momentum segment at a.off[i] of the
+// flat buffers. Any n and any offset: a thread's 4 elements go through 16-byte accesses when all
+// four exist and the segment and the gradient are 16-byte aligned, else one by one. Arithmetic in
+// shard_sgd_kernel<false>'s order: d = g * scale + wd * w; m = mu * m + d; w -= lr * m.
+__device__ __forceinline__ void sgd32_1(float g, float& w, float& m, float lr, float mu, float wd,
+                                        float scale) {
+  const float d = g * scale + wd * w;
+  m = mu * m + d;
+  w = w - lr * m;
+}
+
+__global__ __launch_bounds__(256) void mt_sgd_f32_kernel(MtArgs a, float* __restrict__ wflat,
+                                                         float* __restrict__ mflat, float lr,
+                                                         const float* lr_ptr, float mu, float wd,
+                                                         float scale) {
+  if (lr_ptr) lr = *lr_ptr;
+  int ti = 0;
+  for (int i = 1; i < a.count; ++i)
+    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
+  const long long n = a.n[ti];
+  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
+  if (j >= n) return;
+  const float* g = a.ptr[ti] + j;
+  float* w = wflat + a.off[ti] + j;
+  float* m = mflat + a.off[ti] + j;
+  // wflat / mflat are 16-byte aligned (host-checked), so the segment is when its offset is
+  const bool vec = j + 4 <= n && (a.off[ti] & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(a.ptr[ti]) & 15) == 0;
+  if (vec) {
+    const float4 g4 = *reinterpret_cast<const float4*>(g);
+    float4 w4 = *reinterpret_cast<const float4*>(w);
+    float4 m4 = *reinterpret_cast<const float4*>(m);
+    sgd32_1(g4.x, w4.x, m4.x, lr, mu, wd, scale);
+    sgd32_1(g4.y, w4.y, m4.y, lr, mu, wd, scale);
+    sgd32_1(g4.z, w4.z, m4.z, lr, mu, wd, scale);
+    sgd32_1(g4.w, w4.w, m4.w, lr, mu, wd, scale);
+    *reinterpret_cast<float4*>(w) = w4;
+    *reinterpret_cast<float4*>(m) = m4;
+  } else {
+    for (int k = 0; k < 4 && j + k < n; ++k) {
+      float wk = w[k], mk = m[k];
+      sgd32_1(g[k], wk, mk, lr, mu, wd, scale);
+      w[k] = wk;
+      m[k] = mk;
+    }
+  }
+}
+
+// The learning-rate schedule of arena_amd/ops/schedule.py, advanced on the device so a captured
+// step changes its lr from replay to replay. One lane: finds the segment of *step by a linear
+// search over the (at most 64) segments, evaluates it in fp64 exactly as reference_lr does (every
+// operation rounded on its own: no contraction), rounds once to fp32, then counts the step.
+__global__ void lr_schedule_kernel(const long long* __restrict__ seg, int n_seg,
+                                   long long* __restrict__ step, float* __restrict__ lr) {
+  // This unit is built with -ffp-contract=fast, under which the backend fuses a multiply into a
+  // following add whatever `#pragma clang fp contract(off)` or __dmul_rn / __dadd_rn (a plain
+  // `*` / `+` in HIP's headers) say. The empty asm below makes the product an opaque value, so
+  // it is rounded on its own.
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long t = *step;
+  int k = 0;
+  for (int i = 1; i < n_seg; ++i)
+    if (t >= seg[4 * i]) k = i;
+  const long long b = seg[4 * k], e = seg[4 * k + 1];
+  const double lr0 = __longlong_as_double(seg[4 * k + 2]);
+  const double lr1 = __longlong_as_double(seg[4 * k + 3]);
+  double v = lr1;                        // the open-ended last segment holds its lr1
+  if (k < n_seg - 1) {
+    v = lr0;
+    if (lr1 != lr0) {
+      const double frac = (double)(t - b) / (double)(e - b);
+      double rise = (lr1 - lr0) * frac;
+      asm volatile("" : "+v"(rise));
+      v = lr0 + rise;
+    }
+  }
+  *lr = (float)v;
+  *step = t + 1;
 }
 
 }  // namespace
@@ -1436,8 +1520,8 @@ hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const 
 
 // grads[i]: bf16 gradient pointers; offs/ns: segment offsets (multiples of 4) and sizes (n % 4 == 0).
 hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, const long long* ns,
-                               int count, float* master, float* mom, void* wbf, float lr, float mu,
-                               float wd, hipStream_t stream) {
+                               int count, float* master, float* mom, void* wbf, float lr,
+                               const float* lr_ptr, float mu, float wd, hipStream_t stream) {
   for (int base = 0; base < count; base += kMtMax) {
     MtArgs a;
     const int cnt = std::min(kMtMax, count - base);
@@ -1454,7 +1538,7 @@ hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, 
     a.count = cnt;
     if (blocks == 0) continue;
     hipLaunchKernelGGL(mt_sgd_master_kernel, dim3(blocks), dim3(256), 0, stream, a, master, mom,
-                       reinterpret_cast<uint16_t*>(wbf), lr, mu, wd);
+                       reinterpret_cast<uint16_t*>(wbf), lr, lr_ptr, mu, wd);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -1462,17 +1546,51 @@ hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, 
 }
 
 hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
-                           long long n, float lr, float mu, float wd, float scale,
-                           hipStream_t stream) {
+                           long long n, float lr, const float* lr_ptr, float mu, float wd,
+                           float scale, hipStream_t stream) {
   if (n % 4 || (grad_bf16 && !wbf)) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   const long long blocks = std::min<long long>((n + 1023) / 1024, 4096);
   if (grad_bf16)
     hipLaunchKernelGGL(shard_sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, grad,
-                       w32, mom, reinterpret_cast<uint16_t*>(wbf), n, lr, mu, wd, scale);
+                       w32, mom, reinterpret_cast<uint16_t*>(wbf), n, lr, lr_ptr, mu, wd, scale);
   else
     hipLaunchKernelGGL(shard_sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, grad,
-                       w32, mom, nullptr, n, lr, mu, wd, scale);
+                       w32, mom, nullptr, n, lr, lr_ptr, mu, wd, scale);
+  return hipGetLastError();
+}
+
+// grads[i]: fp32 gradient pointers; offs/ns: segment offsets and sizes in w / mom (any values).
+hipError_t arena_mt_sgd_f32(const float* const* grads, const long long* offs, const long long* ns,
+                            int count, float* w, float* mom, float lr, const float* lr_ptr,
+                            float mu, float wd, float scale, hipStream_t stream) {
+  for (int base = 0; base < count; base += kMtMax) {
+    MtArgs a;
+    const int cnt = std::min(kMtMax, count - base);
+    int blocks = 0;
+    for (int i = 0; i < cnt; ++i) {
+      if (ns[base + i] < 0 || offs[base + i] < 0) return hipErrorInvalidValue;
+      a.ptr[i] = const_cast<float*>(grads[base + i]);
+      a.off[i] = offs[base + i];
+      a.n[i] = ns[base + i];
+      a.blk_begin[i] = blocks;
+      blocks += (int)((ns[base + i] + 1023) / 1024);
+    }
+    a.blk_begin[cnt] = blocks;
+    a.count = cnt;
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(mt_sgd_f32_kernel, dim3(blocks), dim3(256), 0, stream, a, w, mom, lr, lr_ptr,
+                       mu, wd, scale);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
+                             hipStream_t stream) {
+  if (n_seg < 1 || n_seg > 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, seg, n_seg, step, lr);
   return hipGetLastError();
 }
 
