@@ -14,6 +14,7 @@ This is the same workload, built for MI355X:
 * by default one static random batch; with ``--data_dir`` / ``--synth_images`` a uint8 dataset
   resident in GPU memory, fed by one kernel at the head of every (captured) step
   (``arena_amd.ops.data.DeviceImageLoader``), with epochs and an ``--eval`` pass over ``val``;
+  ``--distortions`` adds tf_cnn_benchmarks' random resized crop to that kernel;
 * tf_cnn_benchmarks' learning-rate flags (piecewise schedule, warm-up epochs, exponential
   staircase). The schedule advances on the device at the head of every step
   (``arena_amd.ops.schedule.DeviceLR``), inside the captured graph, and counts the measured steps:
@@ -35,6 +36,24 @@ import torch.nn.functional as F
 
 from ..runtime import heartbeat
 from .common import pick_device, share_cpu_threads
+
+
+def pair(text: str):
+    """argparse type of 'LO,HI'."""
+    try:
+        lo, hi = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected LO,HI, got {text!r}")
+    return lo, hi
+
+
+def distort_of(args):
+    """``DeviceImageLoader``'s ``distort`` for the run's flags (None without --distortions)."""
+    if not getattr(args, "distortions", False):
+        return None
+    from ..ops import reference
+    return {"area": args.distortion_area or reference.CROP_AREA,
+            "aspect": args.distortion_aspect or reference.CROP_ASPECT}
 
 
 def parse(argv=None):
@@ -114,7 +133,23 @@ def parse(argv=None):
                     help="with a dataset: train this many epochs (overrides --num_batches)")
     ap.add_argument("--data_seed", type=int, default=0,
                     help="seed of the shuffle, the crops / flips and the synthetic images")
+    ap.add_argument("--distortions", action="store_true",
+                    help="with a dataset: random resized crop (tf_cnn_benchmarks' --distortions "
+                         "without its colour distortion): each image is a box of random area and "
+                         "aspect ratio, resized to image_size by the input kernel. Off by default "
+                         "(tf_cnn_benchmarks defaults it to on)")
+    ap.add_argument("--distortion_area", type=pair, default=None, metavar="LO,HI",
+                    help="the box's share of the stored image's area (default 0.05,1.0)")
+    ap.add_argument("--distortion_aspect", type=pair, default=None, metavar="LO,HI",
+                    help="the box's width / height (default 0.75,1.33)")
     args = ap.parse_args(argv)
+    if args.distortions or args.distortion_area or args.distortion_aspect:
+        if not args.distortions:
+            ap.error("--distortion_area / --distortion_aspect need --distortions")
+        if not has_data(args):
+            ap.error("--distortions needs --data_dir or --synth_images")
+        if args.eval:
+            ap.error("--distortions does not apply to --eval (evaluation takes the centre crop)")
     if not 0.0 <= args.label_smoothing <= 1.0:
         ap.error("--label_smoothing must lie in [0, 1]")
     if args.data_dir and args.synth_images:
@@ -215,9 +250,13 @@ def make_loader(args, dev, rank, model, data, train):
     im, lb, meta, _ = data
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     s2d = args.data_format == "NHWC" and model.takes_s2d(dev, dtype)
-    return DeviceImageLoader(im, lb, args.batch_size, args.image_size, train=train,
-                             seed=args.data_seed, stream=rank, mean=meta["mean"], std=meta["std"],
-                             layout="s2d" if s2d else "nhwc", dtype=dtype)
+    try:
+        return DeviceImageLoader(im, lb, args.batch_size, args.image_size, train=train,
+                                 seed=args.data_seed, stream=rank, mean=meta["mean"],
+                                 std=meta["std"], layout="s2d" if s2d else "nhwc", dtype=dtype,
+                                 distort=distort_of(args) if train else None)
+    except ValueError as e:
+        raise SystemExit(f"image loader: {e}")
 
 
 def build_model(args, dev):
@@ -448,7 +487,8 @@ def main(argv=None) -> int:
         loader = make_loader(args, dev, rank, model, data, train=True)
         x, y = loader.out, loader.labels_out
         ep_loss = torch.zeros((), dtype=torch.float32, device=dev)
-        data_name = f"{data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size})"
+        data_name = (f"{data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size}"
+                     f"{' distorted' if loader.boxes is not None else ''})")
     head = stats = None
     if args.label_smoothing != 0.0 or args.print_training_accuracy:
         # [kept, top-1, top-5, invalid labels], added to by the loss kernels on the device (so a
@@ -580,6 +620,8 @@ def main(argv=None) -> int:
                             "last_epoch_loss": round(float(ep_loss) / max(ep_steps, 1), 4)})
                 if counts is not None:
                     res["kept"] = counts[0]
+                if loader.boxes is not None:
+                    res.update({"distortions": True, "crop_boxes": loader.boxes.shape[0]})
             print(json.dumps(res), flush=True)
     if rank == 0 and os.environ.get("ARENA_CONV_LOG"):
         from ..ops import conv

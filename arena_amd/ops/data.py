@@ -2,13 +2,15 @@
 device cursor select the rows, and one HIP kernel (``csrc/ops/data_kernels.hip``) writes the
 cropped, flipped, normalised batch -- in the stem's space-to-depth layout when the model takes it.
 No host work per step: ``next()`` is one launch that a captured graph replays, batch k, k+1, ....
+With ``distort`` the window is a random box of random area and aspect ratio, resized to the crop by
+a second kernel of the same file (random resized crop).
 
 GPU tensors go to the extension (raises if it is missing), CPU tensors to the bit-compatible
-reference (``ops/reference.py image_batch``).
+reference (``ops/reference.py image_batch`` / ``image_batch_resized``).
 """
 from __future__ import annotations
 
-from typing import Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -23,6 +25,19 @@ LAYOUTS = {"s2d": 0, "nhwc": 1}
 
 def _impl(t: Tensor):
     return _ext.load() if t.is_cuda else reference
+
+
+def distort_ranges(distort) -> Optional[dict]:
+    """``distort`` (None / False, True or ``{"area": (lo, hi), "aspect": (lo, hi)}``) -> the two
+    ranges as lists, or None."""
+    if distort is None or distort is False:
+        return None
+    if distort is True:
+        distort = {}
+    if not isinstance(distort, dict) or set(distort) - {"area", "aspect"}:
+        raise ValueError("distort must be None, True or a dict with 'area' and / or 'aspect'")
+    return {"area": [float(v) for v in distort.get("area", reference.CROP_AREA)],
+            "aspect": [float(v) for v in distort.get("aspect", reference.CROP_ASPECT)]}
 
 
 class DeviceImageLoader:
@@ -43,7 +58,7 @@ class DeviceImageLoader:
     def __init__(self, images: Tensor, labels: Tensor, batch: int, crop: int, *, train: bool = True,
                  seed: int = 0, stream: int = 0, mean: Sequence[float] = IMAGENET_MEAN,
                  std: Sequence[float] = IMAGENET_STD, layout: str = "nhwc",
-                 dtype: torch.dtype = torch.bfloat16):
+                 dtype: torch.dtype = torch.bfloat16, distort=None):
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 \
                 or images.shape[1] != images.shape[2]:
             raise ValueError("images must be uint8 [n, S, S, 3]")
@@ -61,6 +76,9 @@ class DeviceImageLoader:
             raise ValueError(f"crop must be even and in [2, {S}] (stored size), got {crop}")
         if batch < 1 or n < 1:
             raise ValueError("empty batch or dataset")
+        self.distort = distort_ranges(distort)
+        if self.distort is not None and not train:
+            raise ValueError("distort applies to training; evaluation takes the centre crop")
         dev = images.device
         self.images = images.contiguous()
         self.labels = labels.to(torch.int64).contiguous()
@@ -77,6 +95,11 @@ class DeviceImageLoader:
         self.labels_out = torch.zeros(batch, dtype=torch.int64, device=dev)
         self.rows_out = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.crop_out = torch.zeros(batch, 3, dtype=torch.int32, device=dev)
+        self.boxes = self.box_out = None
+        if self.distort is not None:
+            self.box_out = torch.zeros(batch, 2, dtype=torch.int32, device=dev)
+            self.set_boxes(reference.crop_box_table(S, self.distort["area"],
+                                                    self.distort["aspect"]))
         self.epoch = 0
         self._gen = torch.Generator(device=dev).manual_seed(self.seed * 7919 + self.stream)
         if self.train:
@@ -89,10 +112,17 @@ class DeviceImageLoader:
     def next(self, advance: bool = True) -> Tuple[Tensor, Tensor]:
         """Write the batch at the cursor into the static buffers and (``advance``) move the
         cursor on, all on the device. Returns ``(x or z, labels)``."""
-        _impl(self.images).image_batch(
-            self.images, self.labels, self.perm, self.cursor, self.table, self.out,
-            self.labels_out, self.rows_out, self.crop_out, self.crop, self.crop, self.train,
-            self.seed, self.stream, LAYOUTS[self.layout], bool(advance))
+        if self.boxes is None:
+            _impl(self.images).image_batch(
+                self.images, self.labels, self.perm, self.cursor, self.table, self.out,
+                self.labels_out, self.rows_out, self.crop_out, self.crop, self.crop, self.train,
+                self.seed, self.stream, LAYOUTS[self.layout], bool(advance))
+        else:
+            _impl(self.images).image_batch_resized(
+                self.images, self.labels, self.perm, self.cursor, self.table, self.out,
+                self.labels_out, self.rows_out, self.crop_out, self.boxes, self.box_out,
+                self.crop, self.crop, self.train, self.seed, self.stream, LAYOUTS[self.layout],
+                bool(advance))
         return self.out, self.labels_out
 
     def new_epoch(self) -> None:
@@ -115,14 +145,34 @@ class DeviceImageLoader:
         self.L = perm.numel()
         self.steps_per_epoch = self.L // self.batch if self.train else -(-self.L // self.batch)
 
+    def set_boxes(self, boxes: Tensor) -> None:
+        """Replace the candidate ``(h, w)`` boxes of a distorting loader (int ``[T, 2]``, ``1 <= T
+        <= 4096``); every entry must lie in ``[2, S]``."""
+        if self.distort is None:
+            raise ValueError("set_boxes needs a loader built with distort")
+        S = self.images.shape[1]
+        if boxes.dim() != 2 or boxes.shape[1] != 2 or boxes.dtype.is_floating_point \
+                or not 1 <= boxes.shape[0] <= reference.MAX_CROP_BOXES:
+            raise ValueError(f"boxes must be integer [T, 2] with 1 <= T <= "
+                             f"{reference.MAX_CROP_BOXES}")
+        if int(boxes.min()) < 2 or int(boxes.max()) > S:
+            raise ValueError(f"box sides must lie in [2, {S}] (stored size)")
+        boxes = boxes.to(device=self.images.device, dtype=torch.int32).contiguous()
+        if self.boxes is not None and boxes.shape == self.boxes.shape:
+            self.boxes.copy_(boxes)    # in place: a captured next() keeps reading this buffer
+        else:
+            self.boxes = boxes.clone()
+
     def state_dict(self) -> dict:
         return {"perm": self.perm.detach().cpu().clone(), "cursor": int(self.cursor.item()),
                 "epoch": self.epoch, "rng": self._gen.get_state().clone(),
-                "seed": self.seed, "stream": self.stream}
+                "seed": self.seed, "stream": self.stream, "distort": distort_ranges(self.distort)}
 
     def load_state_dict(self, sd: dict) -> None:
         if (sd["seed"], sd["stream"]) != (self.seed, self.stream):
             raise ValueError("loader state belongs to another seed / stream")
+        if "distort" in sd and distort_ranges(sd["distort"]) != self.distort:
+            raise ValueError("loader state belongs to another distort setting")
         self.set_permutation(sd["perm"])
         self.cursor.fill_(int(sd["cursor"]))
         self.epoch = int(sd["epoch"])

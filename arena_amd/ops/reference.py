@@ -396,6 +396,18 @@ def image_batch(images, labels, perm, cursor, table, out, labels_out, rows_out, 
     px = images[row.clamp(min=0).view(B, 1, 1), ys.view(B, Hc, 1), xs.view(B, 1, Wc)]
     val = table[torch.arange(3).view(1, 1, 1, 3), px.to(torch.int64)]       # [B, Hc, Wc, 3]
     val = torch.where(valid.view(B, 1, 1, 1), val, torch.zeros_like(val))
+    _image_store(out, val, layout)
+    labels_out.copy_(torch.where(valid, labels.to(torch.int64)[row.clamp(min=0)],
+                                 torch.full_like(row, IMAGE_PAD_LABEL)))
+    rows_out.copy_(row)
+    crop_out.view(B, 3).copy_(torch.stack([y0, x0, flip], dim=1))
+    if advance:
+        cursor.add_(1)
+
+
+def _image_store(out, val, layout):
+    """``val`` [B, Hc, Wc, 3] -> ``out``: x (layout 1) or its space-to-depth z (layout 0)."""
+    B, Hc, Wc = val.shape[:3]
     if layout == 1:
         out.copy_(val.permute(0, 3, 1, 2))
     else:
@@ -405,9 +417,118 @@ def image_batch(images, labels, perm, cursor, table, out, labels_out, rows_out, 
                 ch = s2d_channel(dy, dx, 0)
                 z[..., ch:ch + 3] = val[:, dy::2, dx::2, :]
         out.copy_(z.permute(0, 3, 1, 2))
+
+
+# ------------------------------------------------------------------------------------------------
+# Random resized crop (image_batch_resized_kernel). On top of the definitions above:
+#
+# * the candidates: ``crop_box_table(S, area, aspect)`` lists the (h, w) boxes of a 64 x 32 grid
+#   of (area fraction, aspect ratio) that fit the stored image; draw 3 picks one uniformly, so the
+#   device needs neither a rejection loop nor a transcendental function.
+# * the draws: ``box = uniform_below(h3, T)``, ``(h, w) = boxes[box]`` (clamped to [2, S]), ``y0 =
+#   uniform_below(h0, S - h + 1)``, ``x0 = uniform_below(h1, S - w + 1)``, ``flip = h2 >> 31``.
+# * the resampling: bilinear, half-pixel centres, 8-bit weights, integers only. ``resize_taps``
+#   gives (i0, i1, f) per output index; the byte of a pixel is ``((256-fx)(256-fy) p00 + fx
+#   (256-fy) p01 + (256-fx) fy p10 + fx fy p11 + 32768) >> 16`` and goes through the same table.
+#   With (h, w) == (Hc, Wc) every f is 0 and i0 is the output index: the fixed crop, exactly.
+# ------------------------------------------------------------------------------------------------
+CROP_AREA = (0.05, 1.0)       # tf_cnn_benchmarks' area_range
+CROP_ASPECT = (0.75, 1.33)    # ... and aspect_ratio_range
+CROP_BOX_GRID = (64, 32)      # area steps x aspect steps
+MAX_CROP_BOXES = 4096         # the launcher's bound on the table length
+
+
+def crop_box_table(S: int, area=CROP_AREA, aspect=CROP_ASPECT) -> torch.Tensor:
+    """int32 [T, 2] candidate (h, w) boxes in source pixels, row-major in (area, aspect) step."""
+    S = int(S)
+    lo, hi = (float(v) for v in area)
+    rlo, rhi = (float(v) for v in aspect)
+    if not (0.0 < lo <= hi <= 1.0):
+        raise ValueError(f"crop_box_table: area range {area} must satisfy 0 < lo <= hi <= 1")
+    if not (0.0 < rlo <= rhi < math.inf):
+        raise ValueError(f"crop_box_table: aspect range {aspect} must satisfy 0 < lo <= hi < inf")
+    na, nr = CROP_BOX_GRID
+    rows = []
+    for i in range(na):
+        a = lo + (hi - lo) * (i + 0.5) / na
+        for j in range(nr):
+            r = math.exp(math.log(rlo) + (math.log(rhi) - math.log(rlo)) * (j + 0.5) / nr)
+            w = math.floor(math.sqrt(a * S * S * r) + 0.5)
+            h = math.floor(math.sqrt(a * S * S / r) + 0.5)
+            if 2 <= h <= S and 2 <= w <= S:
+                rows.append((h, w))
+    if not rows:
+        raise ValueError(f"crop_box_table: no box of area {area} and aspect {aspect} fits "
+                         f"a {S} x {S} image")
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def resize_taps(n_out: int, extent: torch.Tensor):
+    """(i0, i1, f) int64 [B, n_out]: output index o of ``n_out`` reads source indices i0 and i1 of
+    ``extent`` [B] with weights 256 - f and f."""
+    e = extent.to(torch.int64).view(-1, 1)
+    o = torch.arange(n_out, dtype=torch.int64).view(1, n_out)
+    num = ((2 * o + 1) * e - n_out).clamp(min=0)      # num < 0: i0 = 0 and f = 0
+    den = 2 * n_out
+    i0 = num // den
+    f = ((num % den) * 256) // den
+    return i0, torch.minimum(i0 + 1, e - 1), f
+
+
+def image_box_draws(pos: torch.Tensor, S: int, boxes: torch.Tensor, seed: int, stream: int):
+    """(h, w, y0, x0, flip) int64 tensors for batch positions ``pos``."""
+    T = boxes.shape[0]
+    hw = boxes.to(torch.int64)[uniform_below(image_hash(seed, stream, pos, 3), T)].clamp(2, S)
+    h, w = hw[:, 0], hw[:, 1]
+    return (h, w, (image_hash(seed, stream, pos, 0) * (S - h + 1)) >> 32,
+            (image_hash(seed, stream, pos, 1) * (S - w + 1)) >> 32,
+            image_hash(seed, stream, pos, 2) >> 31)
+
+
+def image_batch_resized(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out,
+                        boxes, box_out, crop_h, crop_w, train, seed, stream, layout, advance):
+    """CPU twin of ``arena_image_batch_resized`` (same arguments as the extension's
+    ``image_batch_resized``)."""
+    n, S = images.shape[0], images.shape[1]
+    B, L, Hc, Wc = out.shape[0], perm.numel(), int(crop_h), int(crop_w)
+    if not train:
+        raise ValueError("image_batch_resized: training only")
+    if Hc % 2 or Wc % 2 or not (2 <= Hc <= S and 2 <= Wc <= S):
+        raise ValueError("image_batch_resized: the crop must be even and at most the stored size")
+    if table.dtype != out.dtype or tuple(table.shape) != (3, 256):
+        raise ValueError("image_batch_resized: table must be [3, 256] in out's dtype")
+    if boxes.dtype != torch.int32 or boxes.dim() != 2 or boxes.shape[1] != 2 \
+            or not 1 <= boxes.shape[0] <= MAX_CROP_BOXES:
+        raise ValueError(f"image_batch_resized: boxes must be int32 [T, 2], 1 <= T <= "
+                         f"{MAX_CROP_BOXES}")
+    if box_out.dtype != torch.int32 or box_out.numel() != 2 * B:
+        raise ValueError("image_batch_resized: box_out must be int32 [B, 2]")
+    pos = _cursor_val(cursor, 0) * B + torch.arange(B, dtype=torch.int64)
+    row = perm.to(torch.int64)[pos % L]
+    valid = (row >= 0) & (row < n)
+    row = torch.where(valid, row, torch.full_like(row, -1))
+    h, w, y0, x0, flip = image_box_draws(pos, S, boxes, int(seed) & _M32, int(stream))
+    i0, i1, fy = resize_taps(Hc, h)                                         # [B, Hc]
+    xo = torch.arange(Wc, dtype=torch.int64).view(1, Wc)
+    xs = torch.where(flip.view(B, 1) != 0, Wc - 1 - xo, xo)
+    j0, j1, fx = (t.gather(1, xs) for t in resize_taps(Wc, w))              # [B, Wc]
+    img = images[row.clamp(min=0)]                                          # [B, S, S, 3]
+    bi = torch.arange(B).view(B, 1, 1)
+
+    def tap(i, j):
+        return img[bi, (y0.view(B, 1) + i).view(B, Hc, 1),
+                   (x0.view(B, 1) + j).view(B, 1, Wc)].to(torch.int64)      # [B, Hc, Wc, 3]
+
+    fy, fx = fy.view(B, Hc, 1, 1), fx.view(B, 1, Wc, 1)
+    u = ((256 - fx) * (256 - fy) * tap(i0, j0) + fx * (256 - fy) * tap(i0, j1)
+         + (256 - fx) * fy * tap(i1, j0) + fx * fy * tap(i1, j1) + 32768) >> 16
+    val = table[torch.arange(3).view(1, 1, 1, 3), u]
+    val = torch.where(valid.view(B, 1, 1, 1), val, torch.zeros_like(val))
+    _image_store(out, val, layout)
     labels_out.copy_(torch.where(valid, labels.to(torch.int64)[row.clamp(min=0)],
                                  torch.full_like(row, IMAGE_PAD_LABEL)))
     rows_out.copy_(row)
     crop_out.view(B, 3).copy_(torch.stack([y0, x0, flip], dim=1))
+    box_out.view(B, 2).copy_(torch.stack([h, w], dim=1))
     if advance:
         cursor.add_(1)

@@ -341,6 +341,9 @@ hipError_t arena_conv_wgrad_ex(const void* x, const void* dy, float* ws, void* d
 // csrc/ops/data_kernels.hip
 hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f32, int advance,
                              hipStream_t st);
+hipError_t arena_image_batch_resized(ArenaImageBatch a, const int* boxes, int n_boxes,
+                                     int* box_out, int layout, int out_f32, int advance,
+                                     hipStream_t st);
 
 // csrc/ccl/xgmi_ccl.hip
 hipError_t arena_ccl_malloc(void** p, size_t bytes, int uncached);

@@ -1529,53 +1529,58 @@ Tensor s2d_stem(Tensor x) {
 // layout 0: out = z, bf16 channels_last [B, 16, crop_h/2, crop_w/2]; 1: out = x, bf16 or fp32
 // channels_last [B, 3, crop_h, crop_w]. labels_out int64 [B], rows_out int32 [B], crop_out int32
 // [B, 3]. advance: the cursor += 1 on the stream after the batch kernel.
-void image_batch(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table, Tensor out,
-                 Tensor labels_out, Tensor rows_out, Tensor crop_out, int64_t crop_h,
-                 int64_t crop_w, bool train, int64_t seed, int64_t stream, int64_t layout,
-                 bool advance) {
+// image_batch_args checks these for image_batch and image_batch_resized (`op` names the caller in
+// its messages).
+static ArenaImageBatch image_batch_args(const char* op, const Tensor& images, const Tensor& labels,
+                                        const Tensor& perm, const Tensor& cursor,
+                                        const Tensor& table, const Tensor& out,
+                                        const Tensor& labels_out, const Tensor& rows_out,
+                                        const Tensor& crop_out, int64_t crop_h, int64_t crop_w,
+                                        bool train, int64_t seed, int64_t stream, int64_t layout) {
+  const std::string operand = std::string(op) + " operand";
   for (auto* t : {&images, &labels, &perm, &cursor, &table, &labels_out, &rows_out, &crop_out})
-    check_dev(*t, "image_batch operand");
-  TORCH_CHECK(out.is_cuda(), "image_batch: out must be a GPU tensor");
+    check_dev(*t, operand.c_str());
+  TORCH_CHECK(out.is_cuda(), op, ": out must be a GPU tensor");
   for (auto* t : {&labels, &perm, &cursor, &table, &out, &labels_out, &rows_out, &crop_out})
-    TORCH_CHECK(t->device() == images.device(), "image_batch: all tensors on one GPU");
+    TORCH_CHECK(t->device() == images.device(), op, ": all tensors on one GPU");
   TORCH_CHECK(images.scalar_type() == torch::kUInt8 && images.dim() == 4 && images.size(3) == 3 &&
                   images.size(1) == images.size(2) && images.size(0) >= 1,
-              "image_batch: images must be uint8 [n, S, S, 3]");
+              op, ": images must be uint8 [n, S, S, 3]");
   const int64_t n = images.size(0), S = images.size(1), L = perm.numel();
-  TORCH_CHECK(S >= 2 && S <= 16384, "image_batch: stored size must lie in [2, 16384]");
+  TORCH_CHECK(S >= 2 && S <= 16384, op, ": stored size must lie in [2, 16384]");
   TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.dim() == 1 && labels.size(0) == n,
-              "image_batch: labels must be int64 [n]");
+              op, ": labels must be int64 [n]");
   TORCH_CHECK(perm.scalar_type() == torch::kInt32 && perm.dim() == 1 && L >= 1,
-              "image_batch: perm must be a non-empty int32 vector");
+              op, ": perm must be a non-empty int32 vector");
   TORCH_CHECK(cursor.scalar_type() == torch::kInt64 && cursor.numel() == 1,
-              "image_batch: cursor must be one int64");
-  TORCH_CHECK(layout == 0 || layout == 1, "image_batch: layout 0 (s2d) or 1 (nhwc)");
+              op, ": cursor must be one int64");
+  TORCH_CHECK(layout == 0 || layout == 1, op, ": layout 0 (s2d) or 1 (nhwc)");
   TORCH_CHECK(crop_h >= 2 && crop_w >= 2 && crop_h % 2 == 0 && crop_w % 2 == 0 && crop_h <= S &&
                   crop_w <= S,
-              "image_batch: the crop must be even and at most the stored size");
+              op, ": the crop must be even and at most the stored size");
   const bool f32 = out.scalar_type() == torch::kFloat32;
   TORCH_CHECK(out.dim() == 4 && out.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                   (out.scalar_type() == torch::kBFloat16 || (f32 && layout == 1)),
-              "image_batch: out must be channels_last bf16 (or fp32 for nhwc)");
+              op, ": out must be channels_last bf16 (or fp32 for nhwc)");
   const int64_t B = out.size(0);
-  TORCH_CHECK(B >= 1 && B <= 65535, "image_batch: batch must lie in [1, 65535]");
+  TORCH_CHECK(B >= 1 && B <= 65535, op, ": batch must lie in [1, 65535]");
   if (layout == 0) {
     TORCH_CHECK(out.size(1) == 16 && out.size(2) == crop_h / 2 && out.size(3) == crop_w / 2,
-                "image_batch: z must be [B, 16, crop_h / 2, crop_w / 2]");
+                op, ": z must be [B, 16, crop_h / 2, crop_w / 2]");
   } else {
     TORCH_CHECK(out.size(1) == 3 && out.size(2) == crop_h && out.size(3) == crop_w,
-                "image_batch: x must be [B, 3, crop_h, crop_w]");
+                op, ": x must be [B, 3, crop_h, crop_w]");
   }
   TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
-              "image_batch: out must be 16-byte aligned");
+              op, ": out must be 16-byte aligned");
   TORCH_CHECK(table.scalar_type() == out.scalar_type() && table.dim() == 2 && table.size(0) == 3 &&
                   table.size(1) == 256,
-              "image_batch: table must be [3, 256] in out's dtype");
+              op, ": table must be [3, 256] in out's dtype");
   TORCH_CHECK(labels_out.scalar_type() == torch::kInt64 && labels_out.numel() == B &&
                   rows_out.scalar_type() == torch::kInt32 && rows_out.numel() == B &&
                   crop_out.scalar_type() == torch::kInt32 && crop_out.numel() == 3 * B,
-              "image_batch: labels_out int64 [B], rows_out int32 [B], crop_out int32 [B, 3]");
-  TORCH_CHECK(stream >= 0 && stream < (1 << 30), "image_batch: stream must lie in [0, 2^30)");
+              op, ": labels_out int64 [B], rows_out int32 [B], crop_out int32 [B, 3]");
+  TORCH_CHECK(stream >= 0 && stream < (1 << 30), op, ": stream must lie in [0, 2^30)");
   ArenaImageBatch a{};
   a.images = images.data_ptr<uint8_t>();
   a.labels = reinterpret_cast<const long long*>(labels.data_ptr<int64_t>());
@@ -1592,8 +1597,48 @@ void image_batch(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tenso
   a.train = train ? 1 : 0;
   a.seed = (uint32_t)seed;
   a.stream = (int)stream;
-  check_hip(arena_image_batch(a, (int)layout, f32 ? 1 : 0, advance ? 1 : 0, cur_stream()),
+  return a;
+}
+
+void image_batch(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table, Tensor out,
+                 Tensor labels_out, Tensor rows_out, Tensor crop_out, int64_t crop_h,
+                 int64_t crop_w, bool train, int64_t seed, int64_t stream, int64_t layout,
+                 bool advance) {
+  const ArenaImageBatch a =
+      image_batch_args("image_batch", images, labels, perm, cursor, table, out, labels_out,
+                       rows_out, crop_out, crop_h, crop_w, train, seed, stream, layout);
+  check_hip(arena_image_batch(a, (int)layout, out.scalar_type() == torch::kFloat32 ? 1 : 0,
+                              advance ? 1 : 0, cur_stream()),
             "image_batch");
+}
+
+// The training batch with a random resized crop (image_batch_resized_kernel; semantics in
+// ops/reference.py image_batch_resized): image_batch's operands plus boxes int32 [T, 2], the
+// candidate (h, w) in source pixels (1 <= T <= 4096; every side in [2, S]: checked by the loader
+// when it installs the table, clamped by the kernel), and box_out int32 [B, 2], the drawn one.
+void image_batch_resized(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table,
+                         Tensor out, Tensor labels_out, Tensor rows_out, Tensor crop_out,
+                         Tensor boxes, Tensor box_out, int64_t crop_h, int64_t crop_w, bool train,
+                         int64_t seed, int64_t stream, int64_t layout, bool advance) {
+  const char* op = "image_batch_resized";
+  const ArenaImageBatch a =
+      image_batch_args(op, images, labels, perm, cursor, table, out, labels_out, rows_out,
+                       crop_out, crop_h, crop_w, train, seed, stream, layout);
+  TORCH_CHECK(train, op, ": training only (evaluation takes the centre crop)");
+  for (auto* t : {&boxes, &box_out}) {
+    check_dev(*t, "image_batch_resized operand");
+    TORCH_CHECK(t->device() == images.device(), op, ": all tensors on one GPU");
+  }
+  TORCH_CHECK(boxes.scalar_type() == torch::kInt32 && boxes.dim() == 2 && boxes.size(1) == 2 &&
+                  boxes.size(0) >= 1 && boxes.size(0) <= 4096,
+              op, ": boxes must be int32 [T, 2] with 1 <= T <= 4096");
+  TORCH_CHECK(box_out.scalar_type() == torch::kInt32 && box_out.numel() == 2 * (int64_t)a.B,
+              op, ": box_out must be int32 [B, 2]");
+  check_hip(arena_image_batch_resized(a, boxes.data_ptr<int>(), (int)boxes.size(0),
+                                      box_out.data_ptr<int>(), (int)layout,
+                                      out.scalar_type() == torch::kFloat32 ? 1 : 0,
+                                      advance ? 1 : 0, cur_stream()),
+            op);
 }
 
 // The 7x7 stem weight [Cout, C<=4, 7, 7] (fp32 or bf16, any strides) -> its space-to-depth form,
@@ -1986,6 +2031,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx_out"), py::arg("addend"), py::arg("stride"), py::arg("variant"));
   m.def("s2d_stem", &s2d_stem);
   m.def("image_batch", &image_batch);
+  m.def("image_batch_resized", &image_batch_resized);
   m.def("stem_weight", &stem_weight);
   m.def("stem_weight_grad", &stem_weight_grad);
   m.def("bn_bwd", &bn_bwd, py::arg("dy"), py::arg("mask"), py::arg("x"), py::arg("mean"),

@@ -15,6 +15,8 @@
 //   out pixel (y, x, c) = table[c][img[row][y0 + y][x0 + (flip ? Wc - 1 - x : x)][c]]
 // table is 3 x 256 values of the output dtype, built once on the host from mean and std, so the
 // kernel and the reference cannot round differently.
+// image_batch_resized_kernel (below) is the training batch with a random resized crop in place of
+// the fixed window.
 #include "common.h"
 
 namespace {
@@ -121,9 +123,171 @@ __global__ __launch_bounds__(256) void image_batch_kernel(const ArenaImageBatch 
   }
 }
 
+// ---- random resized crop: a box of random area and aspect ratio, resized to Hc x Wc ----
+//   box = draw(3, T), (h, w) = boxes[box] clamped to [2, S], y0 = draw(0, S - h + 1),
+//   x0 = draw(1, S - w + 1), flip = hash(2) >> 31
+//   output row y reads box rows i0, i1 with weights 256 - f, f (image_tap: bilinear, half-pixel
+//   centres, 8-bit weights); columns alike, of xs = flip ? Wc - 1 - x : x
+//   u = ((256-fx)(256-fy) p00 + fx (256-fy) p01 + (256-fx) fy p10 + fx fy p11 + 32768) >> 16
+//   out pixel (y, x, c) = table[c][u]
+// Integers only (all below 2^32 for S <= 16384), so the CPU twin (reference.py
+// image_batch_resized) matches bit for bit; with (h, w) == (Hc, Wc) every f is 0 and i0 = y: the
+// fixed crop above.
+struct ImageBox {
+  long long row;   // dataset row, -1: padding
+  int y0, x0, flip, h, w;
+};
+
+// The same for every thread of a block, as image_row.
+__device__ __forceinline__ ImageBox image_box(const ArenaImageBatch& a, const int* boxes,
+                                              int n_boxes, int r) {
+  ImageBox o;
+  const unsigned long long pos = (unsigned long long)a.cursor[0] * (unsigned long long)a.B + r;
+  o.row = a.perm[pos % (unsigned long long)a.L];
+  const uint32_t lo = (uint32_t)pos, hi = (uint32_t)(pos >> 32);
+  const uint32_t st = (uint32_t)a.stream * 4u;
+  const uint32_t t = __umulhi(arena::hash4(a.seed, st + 3u, lo, hi), (uint32_t)n_boxes);
+  // the loader checks the table; a stray entry is clamped, so no tap can leave the image
+  o.h = min(max(boxes[2 * t], 2), a.S);
+  o.w = min(max(boxes[2 * t + 1], 2), a.S);
+  o.y0 = (int)__umulhi(arena::hash4(a.seed, st + 0u, lo, hi), (uint32_t)(a.S - o.h + 1));
+  o.x0 = (int)__umulhi(arena::hash4(a.seed, st + 1u, lo, hi), (uint32_t)(a.S - o.w + 1));
+  o.flip = (int)(arena::hash4(a.seed, st + 2u, lo, hi) >> 31);
+  if (o.row < 0 || o.row >= a.n) o.row = -1;
+  return o;
+}
+
+struct ImageTap {
+  uint32_t i0, i1, f;   // source indices in [0, extent) and the weight of i1 (of 256)
+};
+
+// Output index o of n reads a source of `extent` samples: i0 <= extent - 1 because
+// (2 o + 1) extent - n < 2 n extent.
+__device__ __forceinline__ ImageTap image_tap(int o, int n, int extent) {
+  ImageTap t;
+  const int num = (2 * o + 1) * extent - n;
+  if (num < 0) {
+    t.i0 = 0u;
+    t.f = 0u;
+  } else {
+    const uint32_t den = 2u * (uint32_t)n;
+    t.i0 = (uint32_t)num / den;
+    t.f = (((uint32_t)num - t.i0 * den) * 256u) / den;
+  }
+  t.i1 = min(t.i0 + 1u, (uint32_t)extent - 1u);
+  return t;
+}
+
+// Grid, LDS table, quad per thread, output forms and padding rows as image_batch_kernel. Each of
+// the quad's 4 pixels reads its own 4 taps of 3 bytes (a box larger than the crop shares none),
+// all 48 loads issued before the first table lookup.
+template <typename T, int LAYOUT>
+__global__ __launch_bounds__(256) void image_batch_resized_kernel(const ArenaImageBatch a,
+                                                                  const int* boxes, int n_boxes,
+                                                                  int* box_out) {
+  __shared__ T tab[3 * 256];
+  for (int e = threadIdx.x; e < 3 * 256; e += 256) tab[e] = ((const T*)a.table)[e];
+  const int b = blockIdx.y;
+  const ImageBox ib = image_box(a, boxes, n_boxes, b);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.labels_out[b] = ib.row >= 0 ? a.labels[ib.row] : -100ll;
+    a.rows_out[b] = (int)ib.row;
+    a.crop_out[3 * b + 0] = ib.y0;
+    a.crop_out[3 * b + 1] = ib.x0;
+    a.crop_out[3 * b + 2] = ib.flip;
+    box_out[2 * b + 0] = ib.h;
+    box_out[2 * b + 1] = ib.w;
+  }
+  __syncthreads();
+  const int Hz = a.Hc >> 1, Wz = a.Wc >> 1;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= Hz * Wz) return;
+  const int i = q / Wz, j = q - i * Wz;
+  T v[12];   // [dy][dx][c]
+  if (ib.row >= 0) {
+    const uint8_t* img = a.images + (size_t)ib.row * ((size_t)a.S * a.S * 3);
+    ImageTap ty[2], tx[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      ty[d] = image_tap(2 * i + d, a.Hc, ib.h);
+      tx[d] = image_tap(ib.flip ? a.Wc - 1 - 2 * j - d : 2 * j + d, a.Wc, ib.w);
+    }
+    uint32_t p[2][2][4][3];   // [dy][dx][tap 00, 01, 10, 11][c]
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const uint32_t r0 = ((uint32_t)ib.y0 + ty[dy].i0) * (uint32_t)a.S + (uint32_t)ib.x0;
+      const uint32_t r1 = ((uint32_t)ib.y0 + ty[dy].i1) * (uint32_t)a.S + (uint32_t)ib.x0;
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const uint8_t* t00 = img + (r0 + tx[dx].i0) * 3u;
+        const uint8_t* t01 = img + (r0 + tx[dx].i1) * 3u;
+        const uint8_t* t10 = img + (r1 + tx[dx].i0) * 3u;
+        const uint8_t* t11 = img + (r1 + tx[dx].i1) * 3u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          p[dy][dx][0][c] = t00[c];
+          p[dy][dx][1][c] = t01[c];
+          p[dy][dx][2][c] = t10[c];
+          p[dy][dx][3][c] = t11[c];
+        }
+      }
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+#pragma unroll
+      for (int dx = 0; dx < 2; ++dx) {
+        const uint32_t fy = ty[dy].f, fx = tx[dx].f;
+        const uint32_t w00 = (256u - fx) * (256u - fy), w01 = fx * (256u - fy);
+        const uint32_t w10 = (256u - fx) * fy, w11 = fx * fy;   // the four sum to 65536
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const uint32_t u = (w00 * p[dy][dx][0][c] + w01 * p[dy][dx][1][c] +
+                              w10 * p[dy][dx][2][c] + w11 * p[dy][dx][3][c] + 32768u) >> 16;
+          v[dy * 6 + dx * 3 + c] = tab[c * 256 + u];
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = (T)0;
+  }
+  if constexpr (LAYOUT == 0) {
+    static_assert(sizeof(T) == 2, "the space-to-depth tensor is bf16");
+    uint4 o0, o1;
+    o0.x = v[0] | ((uint32_t)v[1] << 16); o0.y = v[2] | ((uint32_t)v[3] << 16);
+    o0.z = v[4] | ((uint32_t)v[5] << 16); o0.w = v[6] | ((uint32_t)v[7] << 16);
+    o1.x = v[8] | ((uint32_t)v[9] << 16); o1.y = v[10] | ((uint32_t)v[11] << 16);
+    o1.z = 0u; o1.w = 0u;
+    uint4* dst = reinterpret_cast<uint4*>((uint16_t*)a.out + ((size_t)b * Hz * Wz + q) * 16);
+    dst[0] = o0;
+    dst[1] = o1;
+  } else {
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+      const size_t e = (((size_t)b * a.Hc + 2 * i + dy) * a.Wc + 2 * j) * 3;
+      if constexpr (sizeof(T) == 2) {
+        uint32_t* dst = reinterpret_cast<uint32_t*>((uint16_t*)a.out + e);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          dst[k] = (uint32_t)v[dy * 6 + 2 * k] | ((uint32_t)v[dy * 6 + 2 * k + 1] << 16);
+      } else {
+        float2* dst = reinterpret_cast<float2*>((float*)a.out + e);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dst[k] = make_float2(v[dy * 6 + 2 * k], v[dy * 6 + 2 * k + 1]);
+      }
+    }
+  }
+}
+
 // A launch of its own, in stream order after the batch kernel: no block of that launch can see
 // the advanced cursor.
 __global__ void image_cursor_kernel(long long* cursor) { cursor[0] += 1; }
+
+bool image_batch_args_ok(const ArenaImageBatch& a, int layout, int out_f32) {
+  return !(a.B < 1 || a.B > 65535 || a.n < 1 || a.L < 1 || a.S < 2 || a.S > 16384 || a.Hc < 2 ||
+           a.Wc < 2 || (a.Hc & 1) || (a.Wc & 1) || a.Hc > a.S || a.Wc > a.S || a.stream < 0 ||
+           a.stream >= (1 << 30) || layout < 0 || layout > 1 || (layout == 0 && out_f32));
+}
 
 }  // namespace
 
@@ -131,10 +295,7 @@ __global__ void image_cursor_kernel(long long* cursor) { cursor[0] += 1; }
 // else bf16. advance: add 1 to the device cursor after the batch is written.
 extern "C" hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f32, int advance,
                                         hipStream_t st) {
-  if (a.B < 1 || a.B > 65535 || a.n < 1 || a.L < 1 || a.S < 2 || a.S > 16384 || a.Hc < 2 ||
-      a.Wc < 2 || (a.Hc & 1) || (a.Wc & 1) || a.Hc > a.S || a.Wc > a.S || a.stream < 0 ||
-      a.stream >= (1 << 30) || layout < 0 || layout > 1 || (layout == 0 && out_f32))
-    return hipErrorInvalidValue;
+  if (!image_batch_args_ok(a, layout, out_f32)) return hipErrorInvalidValue;
   const int quads = (a.Hc / 2) * (a.Wc / 2);
   const dim3 g((unsigned)((quads + 255) / 256), (unsigned)a.B);
   if (layout == 0)
@@ -143,6 +304,30 @@ extern "C" hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f
     hipLaunchKernelGGL((image_batch_kernel<float, 1>), g, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((image_batch_kernel<uint16_t, 1>), g, dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !advance) return e;
+  hipLaunchKernelGGL(image_cursor_kernel, dim3(1), dim3(1), 0, st, a.cursor);
+  return hipGetLastError();
+}
+
+// The training batch with a random resized crop (a.train must be 1): boxes [n_boxes][2] are the
+// candidate (h, w) in source pixels, box_out [B][2] receives the drawn one. Otherwise as above.
+extern "C" hipError_t arena_image_batch_resized(ArenaImageBatch a, const int* boxes, int n_boxes,
+                                                int* box_out, int layout, int out_f32,
+                                                int advance, hipStream_t st) {
+  if (!image_batch_args_ok(a, layout, out_f32) || !a.train || n_boxes < 1 || n_boxes > 4096)
+    return hipErrorInvalidValue;
+  const int quads = (a.Hc / 2) * (a.Wc / 2);
+  const dim3 g((unsigned)((quads + 255) / 256), (unsigned)a.B);
+  if (layout == 0)
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 0>), g, dim3(256), 0, st, a, boxes,
+                       n_boxes, box_out);
+  else if (out_f32)
+    hipLaunchKernelGGL((image_batch_resized_kernel<float, 1>), g, dim3(256), 0, st, a, boxes,
+                       n_boxes, box_out);
+  else
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 1>), g, dim3(256), 0, st, a, boxes,
+                       n_boxes, box_out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || !advance) return e;
   hipLaunchKernelGGL(image_cursor_kernel, dim3(1), dim3(1), 0, st, a.cursor);
