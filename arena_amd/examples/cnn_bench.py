@@ -14,7 +14,8 @@ This is the same workload, built for MI355X:
 * by default one static random batch; with ``--data_dir`` / ``--synth_images`` a uint8 dataset
   resident in GPU memory, fed by one kernel at the head of every (captured) step
   (``arena_amd.ops.data.DeviceImageLoader``), with epochs and an ``--eval`` pass over ``val``;
-  ``--distortions`` adds tf_cnn_benchmarks' random resized crop to that kernel;
+  ``--distortions`` adds tf_cnn_benchmarks' random resized crop to that kernel and
+  ``--distort_color`` its colour distortion (YIQ form);
 * tf_cnn_benchmarks' learning-rate flags (piecewise schedule, warm-up epochs, exponential
   staircase). The schedule advances on the device at the head of every step
   (``arena_amd.ops.schedule.DeviceLR``), inside the captured graph, and counts the measured steps:
@@ -52,8 +53,11 @@ def distort_of(args):
     if not getattr(args, "distortions", False):
         return None
     from ..ops import reference
-    return {"area": args.distortion_area or reference.CROP_AREA,
-            "aspect": args.distortion_aspect or reference.CROP_ASPECT}
+    distort = {"area": args.distortion_area or reference.CROP_AREA,
+               "aspect": args.distortion_aspect or reference.CROP_ASPECT}
+    if getattr(args, "distort_color", False):
+        distort["color"] = True
+    return distort
 
 
 def parse(argv=None):
@@ -134,14 +138,19 @@ def parse(argv=None):
     ap.add_argument("--data_seed", type=int, default=0,
                     help="seed of the shuffle, the crops / flips and the synthetic images")
     ap.add_argument("--distortions", action="store_true",
-                    help="with a dataset: random resized crop (tf_cnn_benchmarks' --distortions "
-                         "without its colour distortion): each image is a box of random area and "
-                         "aspect ratio, resized to image_size by the input kernel. Off by default "
-                         "(tf_cnn_benchmarks defaults it to on)")
+                    help="with a dataset: random resized crop (tf_cnn_benchmarks' --distortions; "
+                         "its colour distortion is --distort_color): each image is a box of "
+                         "random area and aspect ratio, resized to image_size by the input "
+                         "kernel. Off by default (tf_cnn_benchmarks defaults it to on)")
     ap.add_argument("--distortion_area", type=pair, default=None, metavar="LO,HI",
                     help="the box's share of the stored image's area (default 0.05,1.0)")
     ap.add_argument("--distortion_aspect", type=pair, default=None, metavar="LO,HI",
                     help="the box's width / height (default 0.75,1.33)")
+    ap.add_argument("--distort_color", action="store_true",
+                    help="with --distortions: tf_cnn_benchmarks' colour distortion in its YIQ "
+                         "form (--distort_color_in_yiq): per image a random brightness (up to "
+                         "32/255), saturation and contrast (0.5 to 1.5 each) and hue rotation (up "
+                         "to 0.2 pi), clipped to the valid range, in the input kernel")
     args = ap.parse_args(argv)
     if args.distortions or args.distortion_area or args.distortion_aspect:
         if not args.distortions:
@@ -150,6 +159,11 @@ def parse(argv=None):
             ap.error("--distortions needs --data_dir or --synth_images")
         if args.eval:
             ap.error("--distortions does not apply to --eval (evaluation takes the centre crop)")
+    if args.distort_color:
+        if args.eval:
+            ap.error("--distort_color does not apply to --eval (evaluation takes the centre crop)")
+        if not args.distortions:
+            ap.error("--distort_color needs --distortions")
     if not 0.0 <= args.label_smoothing <= 1.0:
         ap.error("--label_smoothing must lie in [0, 1]")
     if args.data_dir and args.synth_images:
@@ -488,7 +502,8 @@ def main(argv=None) -> int:
         x, y = loader.out, loader.labels_out
         ep_loss = torch.zeros((), dtype=torch.float32, device=dev)
         data_name = (f"{data[3]} ({meta['n']} images, {meta['size']} -> {args.image_size}"
-                     f"{' distorted' if loader.boxes is not None else ''})")
+                     f"{' distorted' if loader.boxes is not None else ''}"
+                     f"{'+color' if loader.color_table is not None else ''})")
     head = stats = None
     if args.label_smoothing != 0.0 or args.print_training_accuracy:
         # [kept, top-1, top-5, invalid labels], added to by the loss kernels on the device (so a
@@ -622,6 +637,8 @@ def main(argv=None) -> int:
                     res["kept"] = counts[0]
                 if loader.boxes is not None:
                     res.update({"distortions": True, "crop_boxes": loader.boxes.shape[0]})
+                if loader.color_table is not None:
+                    res["distort_color"] = True
             print(json.dumps(res), flush=True)
     if rank == 0 and os.environ.get("ARENA_CONV_LOG"):
         from ..ops import conv

@@ -3,10 +3,12 @@ device cursor select the rows, and one HIP kernel (``csrc/ops/data_kernels.hip``
 cropped, flipped, normalised batch -- in the stem's space-to-depth layout when the model takes it.
 No host work per step: ``next()`` is one launch that a captured graph replays, batch k, k+1, ....
 With ``distort`` the window is a random box of random area and aspect ratio, resized to the crop by
-a second kernel of the same file (random resized crop).
+a second kernel of the same file (random resized crop); with its ``"color"`` key that kernel also
+applies tf_cnn_benchmarks' colour distortion (YIQ form), after a launch that sums each crop's
+channels for the contrast step.
 
 GPU tensors go to the extension (raises if it is missing), CPU tensors to the bit-compatible
-reference (``ops/reference.py image_batch`` / ``image_batch_resized``).
+reference (``ops/reference.py image_batch`` / ``image_batch_resized`` / ``image_batch_color``).
 """
 from __future__ import annotations
 
@@ -27,17 +29,40 @@ def _impl(t: Tensor):
     return _ext.load() if t.is_cuda else reference
 
 
+def color_ranges(color) -> Optional[dict]:
+    """``color`` (None / False, True or a dict with any of ``brightness`` (largest |delta| in
+    [0, 1]), ``saturation`` (lo, hi), ``hue`` (largest |angle| in radians) and ``contrast``
+    (lo, hi)) -> the four ranges, or None."""
+    if color is None or color is False:
+        return None
+    if color is True:
+        color = {}
+    if not isinstance(color, dict) or set(color) - {"brightness", "saturation", "hue", "contrast"}:
+        raise ValueError("distort['color'] must be True or a dict with 'brightness', "
+                         "'saturation', 'hue' and / or 'contrast'")
+    return {"brightness": float(color.get("brightness", reference.COLOR_BRIGHTNESS)),
+            "saturation": [float(v) for v in color.get("saturation", reference.COLOR_SATURATION)],
+            "hue": float(color.get("hue", reference.COLOR_HUE)),
+            "contrast": [float(v) for v in color.get("contrast", reference.COLOR_CONTRAST)]}
+
+
 def distort_ranges(distort) -> Optional[dict]:
-    """``distort`` (None / False, True or ``{"area": (lo, hi), "aspect": (lo, hi)}``) -> the two
-    ranges as lists, or None."""
+    """``distort`` (None / False, True or ``{"area": (lo, hi), "aspect": (lo, hi), "color":
+    ...}``) -> the two ranges as lists, plus the colour ranges (``color_ranges``) when the colour
+    distortion is on; or None."""
     if distort is None or distort is False:
         return None
     if distort is True:
         distort = {}
-    if not isinstance(distort, dict) or set(distort) - {"area", "aspect"}:
-        raise ValueError("distort must be None, True or a dict with 'area' and / or 'aspect'")
-    return {"area": [float(v) for v in distort.get("area", reference.CROP_AREA)],
-            "aspect": [float(v) for v in distort.get("aspect", reference.CROP_ASPECT)]}
+    if not isinstance(distort, dict) or set(distort) - {"area", "aspect", "color"}:
+        raise ValueError("distort must be None, True or a dict with 'area', 'aspect' and / or "
+                         "'color'")
+    out = {"area": [float(v) for v in distort.get("area", reference.CROP_AREA)],
+           "aspect": [float(v) for v in distort.get("aspect", reference.CROP_ASPECT)]}
+    color = color_ranges(distort.get("color"))
+    if color is not None:
+        out["color"] = color
+    return out
 
 
 class DeviceImageLoader:
@@ -48,6 +73,13 @@ class DeviceImageLoader:
     flip per image, drawn from ``(seed, stream, position)`` alone. ``train=False``: rows in order,
     centre crop, ``ceil(L / B)`` batches whose tail is padded with label -100 (``cross_entropy``'s
     ``ignore_index``). ``stream`` separates the draws of data-parallel ranks.
+
+    ``distort`` (training only): ``True`` or ``{"area": (lo, hi), "aspect": (lo, hi)}`` takes a
+    random box of that share of the area and that width / height instead of the fixed window and
+    resizes it to the crop (``box_out`` int32 ``[B, 2]``: the drawn ``(h, w)``). Its key
+    ``"color"`` (``True`` for tf_cnn_benchmarks' ranges, or a dict: ``color_ranges``) adds a random
+    brightness, saturation, hue and contrast per image, clipped to the byte range (``color_out``
+    int32 ``[B, 3]``: matrix index, contrast in 1/256ths, brightness in bytes).
 
     ``layout="s2d"`` yields ``z`` bf16 ``[B, 16, crop/2, crop/2]`` (``ResNet.forward(z,
     s2d=True)``), ``"nhwc"`` yields ``x`` ``[B, 3, crop, crop]`` in ``dtype``; both channels_last.
@@ -100,6 +132,14 @@ class DeviceImageLoader:
             self.box_out = torch.zeros(batch, 2, dtype=torch.int32, device=dev)
             self.set_boxes(reference.crop_box_table(S, self.distort["area"],
                                                     self.distort["aspect"]))
+        self.color_table = self.color_out = self.color_sums = self.color_q = None
+        if self.distort is not None and "color" in self.distort:
+            col = self.distort["color"]
+            self.color_q = reference.color_quantised_ranges(col["brightness"], col["contrast"])
+            self.color_out = torch.zeros(batch, 3, dtype=torch.int32, device=dev)
+            self.color_sums = torch.zeros(batch, reference.image_sum_blocks(crop, crop), 3,
+                                          dtype=torch.int32, device=dev)
+            self.set_color_table(reference.color_matrix_table(col["saturation"], col["hue"]))
         self.epoch = 0
         self._gen = torch.Generator(device=dev).manual_seed(self.seed * 7919 + self.stream)
         if self.train:
@@ -117,6 +157,13 @@ class DeviceImageLoader:
                 self.images, self.labels, self.perm, self.cursor, self.table, self.out,
                 self.labels_out, self.rows_out, self.crop_out, self.crop, self.crop, self.train,
                 self.seed, self.stream, LAYOUTS[self.layout], bool(advance))
+        elif self.color_table is not None:
+            _impl(self.images).image_batch_color(
+                self.images, self.labels, self.perm, self.cursor, self.table, self.out,
+                self.labels_out, self.rows_out, self.crop_out, self.boxes, self.box_out,
+                self.color_table, self.color_sums, self.color_out, self.crop, self.crop,
+                self.train, self.seed, self.stream, *self.color_q, LAYOUTS[self.layout],
+                bool(advance))
         else:
             _impl(self.images).image_batch_resized(
                 self.images, self.labels, self.perm, self.cursor, self.table, self.out,
@@ -162,6 +209,26 @@ class DeviceImageLoader:
             self.boxes.copy_(boxes)    # in place: a captured next() keeps reading this buffer
         else:
             self.boxes = boxes.clone()
+
+    def set_color_table(self, matrices: Tensor) -> None:
+        """Replace the candidate colour matrices of a loader built with ``distort["color"]`` (int
+        ``[T, 9]``: row-major 3 x 3 in 1/4096ths, ``1 <= T <= 4096``). With the loader's contrast
+        and brightness ranges every pixel's sum must stay inside 32 bits
+        (``reference.color_coefficient_bound``)."""
+        if self.color_q is None:
+            raise ValueError("set_color_table needs a loader built with distort['color']")
+        if matrices.dim() != 2 or matrices.shape[1] != 9 or matrices.dtype.is_floating_point \
+                or not 1 <= matrices.shape[0] <= reference.MAX_COLOR_MATRICES:
+            raise ValueError(f"matrices must be integer [T, 9] with 1 <= T <= "
+                             f"{reference.MAX_COLOR_MATRICES}")
+        if reference.color_coefficient_bound(matrices, *self.color_q) > 2 ** 31 - 1:
+            raise ValueError("these colour matrices with the loader's contrast and brightness "
+                             "ranges overflow the kernel's 32-bit pixel arithmetic")
+        matrices = matrices.to(device=self.images.device, dtype=torch.int32).contiguous()
+        if self.color_table is not None and matrices.shape == self.color_table.shape:
+            self.color_table.copy_(matrices)   # in place: a captured next() keeps reading it
+        else:
+            self.color_table = matrices.clone()
 
     def state_dict(self) -> dict:
         return {"perm": self.perm.detach().cpu().clone(), "cursor": int(self.cursor.item()),

@@ -489,6 +489,16 @@ def image_batch_resized(images, labels, perm, cursor, table, out, labels_out, ro
                         boxes, box_out, crop_h, crop_w, train, seed, stream, layout, advance):
     """CPU twin of ``arena_image_batch_resized`` (same arguments as the extension's
     ``image_batch_resized``)."""
+    _image_batch_resized(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out,
+                         boxes, box_out, crop_h, crop_w, train, seed, stream, layout, advance,
+                         None)
+
+
+def _image_batch_resized(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out,
+                         boxes, box_out, crop_h, crop_w, train, seed, stream, layout, advance,
+                         color):
+    """``color``: None, or the function of (u [B, Hc, Wc, 3] int64, zero in padding rows; pos) that
+    distorts the resampled bytes (``image_batch_color``, below)."""
     n, S = images.shape[0], images.shape[1]
     B, L, Hc, Wc = out.shape[0], perm.numel(), int(crop_h), int(crop_w)
     if not train:
@@ -522,6 +532,8 @@ def image_batch_resized(images, labels, perm, cursor, table, out, labels_out, ro
     fy, fx = fy.view(B, Hc, 1, 1), fx.view(B, 1, Wc, 1)
     u = ((256 - fx) * (256 - fy) * tap(i0, j0) + fx * (256 - fy) * tap(i0, j1)
          + (256 - fx) * fy * tap(i1, j0) + fx * fy * tap(i1, j1) + 32768) >> 16
+    if color is not None:
+        u = color(torch.where(valid.view(B, 1, 1, 1), u, torch.zeros_like(u)), pos)
     val = table[torch.arange(3).view(1, 1, 1, 3), u]
     val = torch.where(valid.view(B, 1, 1, 1), val, torch.zeros_like(val))
     _image_store(out, val, layout)
@@ -532,3 +544,156 @@ def image_batch_resized(images, labels, perm, cursor, table, out, labels_out, ro
     box_out.view(B, 2).copy_(torch.stack([h, w], dim=1))
     if advance:
         cursor.add_(1)
+
+
+# ------------------------------------------------------------------------------------------------
+# Colour distortion (image_batch_color_kernel): tf_cnn_benchmarks' distort_color in its YIQ form,
+# between the resampled byte ``u`` above and the table lookup. In [0, 1] it is brightness (add d),
+# saturation s and hue rotation t as one linear map ``M = Y^-1 diag(1, s R(t)) Y`` (Y: RGB -> YIQ),
+# contrast ``(x - mu) k + mu`` about the per-channel mean mu of the image, and a clip to [0, 1].
+# The I and Q rows of Y sum to 0, so ``M (1, 1, 1) = (1, 1, 1)`` and either order of contrast
+# against saturation / hue (tf alternates them with the batch position's parity) is the same map,
+# ``clip(k M x + (1 - k) M mu + d)``. In bytes and integers, on top of the definitions above:
+#
+# * the candidates: ``color_matrix_table(saturation, hue)`` is int32 [T, 9]: ``round(M * 2^12)``,
+#   row-major, over a 32 x 32 grid of (saturation, hue angle) steps, built on the host with cos /
+#   sin. Saturation (1, 1) with hue 0 is exactly ``4096 I``.
+# * the draws: ``color_hash(seed, stream, pos, k) = image_hash(seed ^ COLOR_SEED_SALT, stream,
+#   pos, k)``. ``stream * 4 + k`` of draws 0..3 already fills the 32-bit word, so the colour draws
+#   get a domain of their own through the seed, and draws 0..3 stay what they were. ``m =
+#   uniform_below(c0, T)``, ``k_q = k_lo + uniform_below(c1, k_hi - k_lo + 1)`` (contrast in
+#   1/256ths), ``d_q = uniform_below(c2, 2 D + 1) - D`` (brightness in bytes, ``D = round(255
+#   max_delta)``); ``color_out`` receives (m, k_q, d_q).
+# * per image: ``s_c`` = the sum of u over the ``N = Hc Wc`` resampled, flipped crop pixels (exact
+#   integers: any order of summation gives the same bits), ``A = k_q M_q`` (Q20) and ``b_c = d_q
+#   2^20 + floor((256 - k_q) (sum_c' M_q[c][c'] s_c') / N)``, the product in 64 bits (N <= 2^28 for
+#   S <= 16384 and |256 - k_q| r 255 < 2^31 under the bound below: less than 2^59).
+# * per pixel: ``v_c = clamp((sum_c' A[c][c'] u_c' + b_c + 2^19) >> 20, 0, 255)``, then
+#   ``table[c][v_c]``. A padding row stays a zero image.
+# * rounding: both the division in b_c and the shift in v_c round towards minus infinity (Python's
+#   ``//`` and ``>>``). In C++ ``>>`` of a negative int does so too, ``/`` truncates: the kernel
+#   corrects its quotient when the remainder is negative.
+# * widths: with r the largest sum over a row of |M_q|, |sum A u| <= k_hi r 255 and |b_c| <= D 2^20
+#   + max|256 - k_q| r 255 + 1. Their sum is ``M_q w + d_q 2^20`` (less the floor's fraction) with
+#   ``w = k_q u + (256 - k_q) s / N``, and every channel of w lies in [0, 256 * 255] for k_q <= 256
+#   and in [-(k_q - 256) 255, k_q 255] above, so it is at most ``r 255 max(256, k_hi) + D 2^20 +
+#   1`` in size. ``color_coefficient_bound`` is the larger of the bound on b_c and of that one plus
+#   2^19; the loader refuses ranges for which it passes 2^31 - 1, so a pixel is 32-bit work. tf's
+#   ranges give r = 13319 (3.25) and 1.34e9.
+# ------------------------------------------------------------------------------------------------
+COLOR_BRIGHTNESS = 32.0 / 255.0     # tf_cnn_benchmarks' max_delta
+COLOR_SATURATION = (0.5, 1.5)
+COLOR_HUE = 0.2 * math.pi           # the largest |angle| of the rotation in the IQ plane
+COLOR_CONTRAST = (0.5, 1.5)
+COLOR_MATRIX_GRID = (32, 32)        # saturation steps x hue steps
+MAX_COLOR_MATRICES = 4096           # the launcher's bound on the table length
+MAX_COLOR_CONTRAST_Q = 4096         # ... and on k_q (16.0)
+COLOR_SEED_SALT = 0x636F6C72
+RGB_TO_YIQ = ((0.299, 0.587, 0.114), (0.5959, -0.2746, -0.3213), (0.2115, -0.5227, 0.3112))
+
+
+def color_matrix_table(saturation=COLOR_SATURATION, hue=COLOR_HUE) -> torch.Tensor:
+    """int32 [T, 9] candidate matrices ``round(M * 4096)``, row-major in (saturation, hue) step;
+    ``hue`` is the largest |angle| in radians."""
+    slo, shi = (float(v) for v in saturation)
+    hue = float(hue)
+    if not (0.0 <= slo <= shi < math.inf):
+        raise ValueError(f"color_matrix_table: saturation range {saturation} must satisfy "
+                         f"0 <= lo <= hi < inf")
+    if not (0.0 <= hue <= math.pi):
+        raise ValueError(f"color_matrix_table: hue {hue} must lie in [0, pi]")
+    Y = torch.tensor(RGB_TO_YIQ, dtype=torch.float64)
+    Yi = torch.linalg.inv(Y)
+    ns, nh = COLOR_MATRIX_GRID
+    rows = []
+    for i in range(ns):
+        s = slo + (shi - slo) * (i + 0.5) / ns
+        for j in range(nh):
+            t = -hue + 2.0 * hue * (j + 0.5) / nh
+            c, d = s * math.cos(t), s * math.sin(t)
+            R = torch.tensor([[1.0, 0.0, 0.0], [0.0, c, -d], [0.0, d, c]], dtype=torch.float64)
+            rows.append(torch.floor((Yi @ R @ Y) * 4096.0 + 0.5).reshape(9))
+    return torch.stack(rows).to(torch.int32)
+
+
+def color_quantised_ranges(brightness=COLOR_BRIGHTNESS, contrast=COLOR_CONTRAST):
+    """(k_lo, k_hi, D): contrast in 1/256ths and the largest |brightness| in bytes."""
+    clo, chi = (float(v) for v in contrast)
+    brightness = float(brightness)
+    if not (0.0 <= clo <= chi) or math.floor(chi * 256.0 + 0.5) > MAX_COLOR_CONTRAST_Q:
+        raise ValueError(f"color: contrast range {contrast} must satisfy 0 <= lo <= hi <= "
+                         f"{MAX_COLOR_CONTRAST_Q // 256}")
+    if not (0.0 <= brightness <= 1.0):
+        raise ValueError(f"color: brightness {brightness} must lie in [0, 1]")
+    return (math.floor(clo * 256.0 + 0.5), math.floor(chi * 256.0 + 0.5),
+            math.floor(brightness * 255.0 + 0.5))
+
+
+def color_coefficient_bound(matrices: torch.Tensor, k_lo: int, k_hi: int, delta: int) -> int:
+    """The largest |sum A u + b + 2^19| a pixel can reach (see the contract above)."""
+    r = int(matrices.to(torch.int64).abs().view(-1, 3, 3).sum(2).max())
+    b = (delta << 20) + max(abs(256 - k_lo), abs(256 - k_hi)) * r * 255 + 1
+    return max(b, r * 255 * max(256, k_hi) + (delta << 20) + 1 + (1 << 19))
+
+
+def color_hash(seed: int, stream: int, pos: torch.Tensor, k: int) -> torch.Tensor:
+    return image_hash((seed ^ COLOR_SEED_SALT) & _M32, stream, pos, k)
+
+
+def image_color_draws(pos: torch.Tensor, T: int, k_lo: int, k_hi: int, delta: int, seed: int,
+                      stream: int):
+    """(m, k_q, d_q) int64 tensors for batch positions ``pos``."""
+    return (uniform_below(color_hash(seed, stream, pos, 0), T),
+            k_lo + uniform_below(color_hash(seed, stream, pos, 1), k_hi - k_lo + 1),
+            uniform_below(color_hash(seed, stream, pos, 2), 2 * delta + 1) - delta)
+
+
+IMAGE_BLOCK_QUADS = 256             # 2 x 2 pixel quads per block of the batch kernels
+
+
+def image_sum_blocks(crop_h: int, crop_w: int) -> int:
+    """Blocks per image: the length of an image's row of partial channel sums."""
+    return -(-((crop_h // 2) * (crop_w // 2)) // IMAGE_BLOCK_QUADS)
+
+
+def image_batch_color(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out,
+                      boxes, box_out, matrices, sums, color_out, crop_h, crop_w, train, seed,
+                      stream, k_lo, k_hi, delta, layout, advance):
+    """CPU twin of ``arena_image_batch_color`` (same arguments as the extension's
+    ``image_batch_color``): ``image_batch_resized`` with the colour distortion above. ``matrices``
+    int32 [T, 9]; ``sums`` int32 [B, image_sum_blocks, 3] receives the channel sums of each block's
+    quads (quad q = i * (Wc / 2) + j belongs to block q // 256), ``color_out`` int32 [B, 3] the
+    draws."""
+    B, Hc, Wc = out.shape[0], int(crop_h), int(crop_w)
+    k_lo, k_hi, delta = int(k_lo), int(k_hi), int(delta)
+    T, nblk = matrices.shape[0], image_sum_blocks(Hc, Wc)
+    if matrices.dtype != torch.int32 or matrices.dim() != 2 or matrices.shape[1] != 9 \
+            or not 1 <= T <= MAX_COLOR_MATRICES:
+        raise ValueError(f"image_batch_color: matrices must be int32 [T, 9], 1 <= T <= "
+                         f"{MAX_COLOR_MATRICES}")
+    if not (0 <= k_lo <= k_hi <= MAX_COLOR_CONTRAST_Q and 0 <= delta <= 255):
+        raise ValueError("image_batch_color: contrast or brightness out of range")
+    if sums.dtype != torch.int32 or sums.numel() != B * nblk * 3:
+        raise ValueError("image_batch_color: sums must be int32 [B, blocks per image, 3]")
+    if color_out.dtype != torch.int32 or color_out.numel() != 3 * B:
+        raise ValueError("image_batch_color: color_out must be int32 [B, 3]")
+
+    def color(u, pos):
+        m, kq, dq = image_color_draws(pos, T, k_lo, k_hi, delta, int(seed) & _M32, int(stream))
+        color_out.view(B, 3).copy_(torch.stack([m, kq, dq], dim=1))
+        quads = u.view(B, Hc // 2, 2, Wc // 2, 2, 3).sum((2, 4)).view(B, -1, 3)
+        part = torch.zeros(B, nblk * IMAGE_BLOCK_QUADS, 3, dtype=torch.int64)
+        part[:, :quads.shape[1]] = quads
+        part = part.view(B, nblk, IMAGE_BLOCK_QUADS, 3).sum(2)
+        sums.view(B, nblk, 3).copy_(part)
+        s = part.sum(1)                                                     # [B, 3]
+        Mq = matrices.to(torch.int64)[m].view(B, 3, 3)
+        A = kq.view(B, 1, 1) * Mq
+        b = (dq << 20).view(B, 1) + torch.div(
+            (256 - kq).view(B, 1) * (Mq * s.view(B, 1, 3)).sum(2), Hc * Wc, rounding_mode="floor")
+        acc = (A.view(B, 1, 1, 3, 3) * u.view(B, Hc, Wc, 1, 3)).sum(4) + b.view(B, 1, 1, 3)
+        return ((acc + (1 << 19)) >> 20).clamp(0, 255)
+
+    _image_batch_resized(images, labels, perm, cursor, table, out, labels_out, rows_out, crop_out,
+                         boxes, box_out, crop_h, crop_w, train, seed, stream, layout, advance,
+                         color)

@@ -175,6 +175,17 @@ struct ArenaImageBatch {
   int stream;               // draw stream (the data-parallel rank)
 };
 
+// The colour distortion of arena_image_batch_color (semantics: ops/reference.py image_batch_color).
+struct ArenaImageColor {
+  const int* matrices;      // [n_matrices][9]: candidate 3 x 3 colour maps in 1/4096ths, row-major
+  int n_matrices;           // 1 .. 4096
+  int k_lo, k_hi;           // contrast range in 1/256ths, 0 <= k_lo <= k_hi <= 4096
+  int delta;                // largest |brightness| in bytes, 0 .. 255
+  int* sums;                // [B][blocks per image][3]: each block's channel sums (scratch;
+                            // blocks per image = ceil((Hc / 2) (Wc / 2) / 256))
+  int* color_out;           // [B][3]: matrix index, contrast, brightness
+};
+
 // Intra-node xGMI collective (csrc/ccl/xgmi_ccl.hip): every rank's registered buffers, mapped into
 // this process through hipIpc handles (buf[rank] / sig[rank] are the local allocations).
 #define ARENA_CCL_MAX_RANKS 8
@@ -344,6 +355,9 @@ hipError_t arena_image_batch(ArenaImageBatch a, int layout, int out_f32, int adv
 hipError_t arena_image_batch_resized(ArenaImageBatch a, const int* boxes, int n_boxes,
                                      int* box_out, int layout, int out_f32, int advance,
                                      hipStream_t st);
+hipError_t arena_image_batch_color(ArenaImageBatch a, const int* boxes, int n_boxes, int* box_out,
+                                   ArenaImageColor col, int layout, int out_f32, int advance,
+                                   hipStream_t st);
 
 // csrc/ccl/xgmi_ccl.hip
 hipError_t arena_ccl_malloc(void** p, size_t bytes, int uncached);

@@ -1616,6 +1616,22 @@ void image_batch(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tenso
 // ops/reference.py image_batch_resized): image_batch's operands plus boxes int32 [T, 2], the
 // candidate (h, w) in source pixels (1 <= T <= 4096; every side in [2, S]: checked by the loader
 // when it installs the table, clamped by the kernel), and box_out int32 [B, 2], the drawn one.
+// image_box_args checks the two for image_batch_resized and image_batch_color.
+static void image_box_args(const char* op, const ArenaImageBatch& a, const Tensor& images,
+                           const Tensor& boxes, const Tensor& box_out) {
+  TORCH_CHECK(a.train, op, ": training only (evaluation takes the centre crop)");
+  const std::string operand = std::string(op) + " operand";
+  for (auto* t : {&boxes, &box_out}) {
+    check_dev(*t, operand.c_str());
+    TORCH_CHECK(t->device() == images.device(), op, ": all tensors on one GPU");
+  }
+  TORCH_CHECK(boxes.scalar_type() == torch::kInt32 && boxes.dim() == 2 && boxes.size(1) == 2 &&
+                  boxes.size(0) >= 1 && boxes.size(0) <= 4096,
+              op, ": boxes must be int32 [T, 2] with 1 <= T <= 4096");
+  TORCH_CHECK(box_out.scalar_type() == torch::kInt32 && box_out.numel() == 2 * (int64_t)a.B,
+              op, ": box_out must be int32 [B, 2]");
+}
+
 void image_batch_resized(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table,
                          Tensor out, Tensor labels_out, Tensor rows_out, Tensor crop_out,
                          Tensor boxes, Tensor box_out, int64_t crop_h, int64_t crop_w, bool train,
@@ -1624,20 +1640,56 @@ void image_batch_resized(Tensor images, Tensor labels, Tensor perm, Tensor curso
   const ArenaImageBatch a =
       image_batch_args(op, images, labels, perm, cursor, table, out, labels_out, rows_out,
                        crop_out, crop_h, crop_w, train, seed, stream, layout);
-  TORCH_CHECK(train, op, ": training only (evaluation takes the centre crop)");
-  for (auto* t : {&boxes, &box_out}) {
-    check_dev(*t, "image_batch_resized operand");
-    TORCH_CHECK(t->device() == images.device(), op, ": all tensors on one GPU");
-  }
-  TORCH_CHECK(boxes.scalar_type() == torch::kInt32 && boxes.dim() == 2 && boxes.size(1) == 2 &&
-                  boxes.size(0) >= 1 && boxes.size(0) <= 4096,
-              op, ": boxes must be int32 [T, 2] with 1 <= T <= 4096");
-  TORCH_CHECK(box_out.scalar_type() == torch::kInt32 && box_out.numel() == 2 * (int64_t)a.B,
-              op, ": box_out must be int32 [B, 2]");
+  image_box_args(op, a, images, boxes, box_out);
   check_hip(arena_image_batch_resized(a, boxes.data_ptr<int>(), (int)boxes.size(0),
                                       box_out.data_ptr<int>(), (int)layout,
                                       out.scalar_type() == torch::kFloat32 ? 1 : 0,
                                       advance ? 1 : 0, cur_stream()),
+            op);
+}
+
+// The resized training batch with the colour distortion (image_batch_color_kernel; semantics in
+// ops/reference.py image_batch_color): image_batch_resized's operands plus matrices int32 [T, 9]
+// (1 <= T <= 4096; entries checked against the 32-bit pixel arithmetic by the loader when it
+// installs the table), sums int32 [B, blocks per image, 3] (scratch: each block's channel sums),
+// color_out int32 [B, 3] (the drawn matrix index, contrast and brightness), the contrast range
+// k_lo .. k_hi in 1/256ths and the largest |brightness| delta in bytes.
+void image_batch_color(Tensor images, Tensor labels, Tensor perm, Tensor cursor, Tensor table,
+                       Tensor out, Tensor labels_out, Tensor rows_out, Tensor crop_out,
+                       Tensor boxes, Tensor box_out, Tensor matrices, Tensor sums,
+                       Tensor color_out, int64_t crop_h, int64_t crop_w, bool train, int64_t seed,
+                       int64_t stream, int64_t k_lo, int64_t k_hi, int64_t delta, int64_t layout,
+                       bool advance) {
+  const char* op = "image_batch_color";
+  const ArenaImageBatch a =
+      image_batch_args(op, images, labels, perm, cursor, table, out, labels_out, rows_out,
+                       crop_out, crop_h, crop_w, train, seed, stream, layout);
+  image_box_args(op, a, images, boxes, box_out);
+  for (auto* t : {&matrices, &sums, &color_out}) {
+    check_dev(*t, "image_batch_color operand");
+    TORCH_CHECK(t->device() == images.device(), op, ": all tensors on one GPU");
+  }
+  TORCH_CHECK(matrices.scalar_type() == torch::kInt32 && matrices.dim() == 2 &&
+                  matrices.size(1) == 9 && matrices.size(0) >= 1 && matrices.size(0) <= 4096,
+              op, ": matrices must be int32 [T, 9] with 1 <= T <= 4096");
+  const int64_t blocks = ((crop_h / 2) * (crop_w / 2) + 255) / 256;
+  TORCH_CHECK(sums.scalar_type() == torch::kInt32 && sums.numel() == (int64_t)a.B * blocks * 3,
+              op, ": sums must be int32 [B, ", blocks, ", 3]");
+  TORCH_CHECK(color_out.scalar_type() == torch::kInt32 && color_out.numel() == 3 * (int64_t)a.B,
+              op, ": color_out must be int32 [B, 3]");
+  TORCH_CHECK(0 <= k_lo && k_lo <= k_hi && k_hi <= 4096, op,
+              ": contrast must satisfy 0 <= k_lo <= k_hi <= 4096 (1/256ths)");
+  TORCH_CHECK(0 <= delta && delta <= 255, op, ": brightness delta must lie in [0, 255]");
+  ArenaImageColor col{};
+  col.matrices = matrices.data_ptr<int>();
+  col.n_matrices = (int)matrices.size(0);
+  col.k_lo = (int)k_lo; col.k_hi = (int)k_hi; col.delta = (int)delta;
+  col.sums = sums.data_ptr<int>();
+  col.color_out = color_out.data_ptr<int>();
+  check_hip(arena_image_batch_color(a, boxes.data_ptr<int>(), (int)boxes.size(0),
+                                    box_out.data_ptr<int>(), col, (int)layout,
+                                    out.scalar_type() == torch::kFloat32 ? 1 : 0,
+                                    advance ? 1 : 0, cur_stream()),
             op);
 }
 
@@ -2032,6 +2084,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("s2d_stem", &s2d_stem);
   m.def("image_batch", &image_batch);
   m.def("image_batch_resized", &image_batch_resized);
+  m.def("image_batch_color", &image_batch_color);
   m.def("stem_weight", &stem_weight);
   m.def("stem_weight_grad", &stem_weight_grad);
   m.def("bn_bwd", &bn_bwd, py::arg("dy"), py::arg("mask"), py::arg("x"), py::arg("mean"),

@@ -16,7 +16,8 @@
 // table is 3 x 256 values of the output dtype, built once on the host from mean and std, so the
 // kernel and the reference cannot round differently.
 // image_batch_resized_kernel (below) is the training batch with a random resized crop in place of
-// the fixed window.
+// the fixed window and, in two launches, a colour distortion of the resampled bytes (CPU twin:
+// image_batch_color).
 #include "common.h"
 
 namespace {
@@ -178,18 +179,118 @@ __device__ __forceinline__ ImageTap image_tap(int o, int n, int extent) {
   return t;
 }
 
+// ---- colour distortion (tf_cnn_benchmarks' distort_color, YIQ form) on the resampled bytes ----
+//   m = cdraw(0, T), k = k_lo + cdraw(1, k_hi - k_lo + 1), d = cdraw(2, 2 D + 1) - D with
+//   cdraw(i, n) = draw(i, n) under the seed a.seed ^ kColorSeedSalt (draws 0..3 stay as they are)
+//   per image: s_c = sum of u_c over the Hc x Wc crop, A = k M[m] (Q20),
+//              b_c = d 2^20 + floor((256 - k) (M[m] s)_c / (Hc Wc))            (64-bit)
+//   per pixel: v_c = clamp((A u + b + 2^19)_c >> 20, 0, 255), then table[c][v_c]
+// The contract, its rounding rule and the 32-bit width argument: ops/reference.py
+// (image_batch_color, the CPU twin, bit for bit). s_c needs the whole crop before any pixel is
+// written, so a first launch of the same grid stores each block's channel sums (plain stores of
+// integers: nothing to re-zero between replays, no order to depend on) and every block of the
+// second launch adds up its image's row of them.
+constexpr uint32_t kColorSeedSalt = 0x636F6C72u;
+
+struct ImageColorDraw {
+  int m, k, d;
+};
+
+// The same for every thread of a block, as image_box.
+__device__ __forceinline__ ImageColorDraw image_color_draw(const ArenaImageBatch& a,
+                                                           const ArenaImageColor& col, int r) {
+  ImageColorDraw o;
+  const unsigned long long pos = (unsigned long long)a.cursor[0] * (unsigned long long)a.B + r;
+  const uint32_t lo = (uint32_t)pos, hi = (uint32_t)(pos >> 32);
+  const uint32_t seed = a.seed ^ kColorSeedSalt, st = (uint32_t)a.stream * 4u;
+  o.m = (int)__umulhi(arena::hash4(seed, st + 0u, lo, hi), (uint32_t)col.n_matrices);
+  o.k = col.k_lo + (int)__umulhi(arena::hash4(seed, st + 1u, lo, hi),
+                                 (uint32_t)(col.k_hi - col.k_lo + 1));
+  o.d = (int)__umulhi(arena::hash4(seed, st + 2u, lo, hi), (uint32_t)(2 * col.delta + 1)) -
+        col.delta;
+  return o;
+}
+
+// coef[0..8] = A (row-major), coef[9..11] = b for batch row b, computed once per block: every
+// thread adds a share of the image's block sums, threads 0..2 finish one channel each. Ends with
+// a barrier.
+__device__ __forceinline__ void image_color_coefficients(const ArenaImageBatch& a,
+                                                         const ArenaImageColor& col,
+                                                         const ImageColorDraw& cd, int b,
+                                                         int* coef) {
+  __shared__ long long red[4][3];
+  long long s[3] = {0ll, 0ll, 0ll};
+  const int* row = col.sums + (size_t)b * gridDim.x * 3;
+  for (int e = threadIdx.x; e < (int)gridDim.x; e += 256) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s[c] += row[3 * e + c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_down(s[c], off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int c = threadIdx.x;
+    const int* M = col.matrices + 9 * cd.m + 3 * c;
+    long long t = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      t += (long long)M[k] * (red[0][k] + red[1][k] + red[2][k] + red[3][k]);
+      coef[3 * c + k] = cd.k * M[k];
+    }
+    const long long num = (long long)(256 - cd.k) * t, N = (long long)a.Hc * a.Wc;
+    long long quo = num / N;
+    if (num - quo * N < 0) --quo;   // floor, as the reference's //
+    coef[9 + c] = cd.d * (1 << 20) + (int)quo;
+  }
+  __syncthreads();
+}
+
+// The sums launch: col.sums[b][blockIdx.x][c] = the sum of channel c over this block's quads (at
+// most 1024 pixels of at most 255: 32 bits hold it); zero for a padding row.
+__device__ __forceinline__ void image_store_block_sums(uint32_t s[3], int* sums, int b) {
+  __shared__ uint32_t red[4][3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_down(s[c], off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = s[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int c = threadIdx.x;
+    sums[((size_t)b * gridDim.x + blockIdx.x) * 3 + c] =
+        (int)(red[0][c] + red[1][c] + red[2][c] + red[3][c]);
+  }
+}
+
 // Grid, LDS table, quad per thread, output forms and padding rows as image_batch_kernel. Each of
 // the quad's 4 pixels reads its own 4 taps of 3 bytes (a box larger than the crop shares none),
 // all 48 loads issued before the first table lookup.
-template <typename T, int LAYOUT>
+// MODE picks what happens to the resampled byte u: IMAGE_PLAIN looks it up in the table;
+// IMAGE_SUMS (T and LAYOUT unused) only adds it to the block's channel sums and writes no batch;
+// IMAGE_COLOR distorts it with the coefficients made from those sums, then looks it up. One body,
+// so the three cannot resample differently; every difference is an `if constexpr`, and the plain
+// instantiations compile to the instructions they had before the colour distortion existed.
+enum { IMAGE_PLAIN = 0, IMAGE_SUMS = 1, IMAGE_COLOR = 2 };
+
+template <typename T, int LAYOUT, int MODE>
 __global__ __launch_bounds__(256) void image_batch_resized_kernel(const ArenaImageBatch a,
                                                                   const int* boxes, int n_boxes,
-                                                                  int* box_out) {
+                                                                  int* box_out,
+                                                                  const ArenaImageColor col) {
   __shared__ T tab[3 * 256];
-  for (int e = threadIdx.x; e < 3 * 256; e += 256) tab[e] = ((const T*)a.table)[e];
+  __shared__ int coef[MODE == IMAGE_COLOR ? 12 : 1];
+  if constexpr (MODE != IMAGE_SUMS)
+    for (int e = threadIdx.x; e < 3 * 256; e += 256) tab[e] = ((const T*)a.table)[e];
   const int b = blockIdx.y;
   const ImageBox ib = image_box(a, boxes, n_boxes, b);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
+  ImageColorDraw cd{};
+  if constexpr (MODE == IMAGE_COLOR) cd = image_color_draw(a, col, b);
+  if (MODE != IMAGE_SUMS && blockIdx.x == 0 && threadIdx.x == 0) {
     a.labels_out[b] = ib.row >= 0 ? a.labels[ib.row] : -100ll;
     a.rows_out[b] = (int)ib.row;
     a.crop_out[3 * b + 0] = ib.y0;
@@ -197,14 +298,23 @@ __global__ __launch_bounds__(256) void image_batch_resized_kernel(const ArenaIma
     a.crop_out[3 * b + 2] = ib.flip;
     box_out[2 * b + 0] = ib.h;
     box_out[2 * b + 1] = ib.w;
+    if constexpr (MODE == IMAGE_COLOR) {
+      col.color_out[3 * b + 0] = cd.m;
+      col.color_out[3 * b + 1] = cd.k;
+      col.color_out[3 * b + 2] = cd.d;
+    }
   }
-  __syncthreads();
+  if constexpr (MODE == IMAGE_COLOR) image_color_coefficients(a, col, cd, b, coef);
+  if constexpr (MODE == IMAGE_PLAIN) __syncthreads();
   const int Hz = a.Hc >> 1, Wz = a.Wc >> 1;
   const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= Hz * Wz) return;
+  // the sums launch keeps every thread for its reduction
+  if (MODE != IMAGE_SUMS && q >= Hz * Wz) return;
   const int i = q / Wz, j = q - i * Wz;
   T v[12];   // [dy][dx][c]
-  if (ib.row >= 0) {
+  uint32_t ub[12];                 // IMAGE_COLOR: the bytes before the table
+  uint32_t s[3] = {0u, 0u, 0u};    // IMAGE_SUMS: this thread's channel sums
+  if (ib.row >= 0 && (MODE != IMAGE_SUMS || q < Hz * Wz)) {
     const uint8_t* img = a.images + (size_t)ib.row * ((size_t)a.S * a.S * 3);
     ImageTap ty[2], tx[2];
 #pragma unroll
@@ -243,7 +353,28 @@ __global__ __launch_bounds__(256) void image_batch_resized_kernel(const ArenaIma
         for (int c = 0; c < 3; ++c) {
           const uint32_t u = (w00 * p[dy][dx][0][c] + w01 * p[dy][dx][1][c] +
                               w10 * p[dy][dx][2][c] + w11 * p[dy][dx][3][c] + 32768u) >> 16;
-          v[dy * 6 + dx * 3 + c] = tab[c * 256 + u];
+          if constexpr (MODE == IMAGE_SUMS)
+            s[c] += u;
+          else if constexpr (MODE == IMAGE_COLOR)
+            ub[dy * 6 + dx * 3 + c] = u;
+          else
+            v[dy * 6 + dx * 3 + c] = tab[c * 256 + u];
+        }
+      }
+    }
+    if constexpr (MODE == IMAGE_COLOR) {
+      int A[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) A[k] = coef[k];
+#pragma unroll
+      for (int px = 0; px < 4; ++px) {
+        const int u0 = (int)ub[3 * px], u1 = (int)ub[3 * px + 1], u2 = (int)ub[3 * px + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          // >> of a negative sum rounds towards minus infinity, as the reference's
+          const int acc = A[3 * c] * u0 + A[3 * c + 1] * u1 + A[3 * c + 2] * u2 + A[9 + c] +
+                          (1 << 19);
+          v[3 * px + c] = tab[c * 256 + min(max(acc >> 20, 0), 255)];
         }
       }
     }
@@ -251,7 +382,9 @@ __global__ __launch_bounds__(256) void image_batch_resized_kernel(const ArenaIma
 #pragma unroll
     for (int k = 0; k < 12; ++k) v[k] = (T)0;
   }
-  if constexpr (LAYOUT == 0) {
+  if constexpr (MODE == IMAGE_SUMS) {
+    image_store_block_sums(s, col.sums, b);
+  } else if constexpr (LAYOUT == 0) {
     static_assert(sizeof(T) == 2, "the space-to-depth tensor is bf16");
     uint4 o0, o1;
     o0.x = v[0] | ((uint32_t)v[1] << 16); o0.y = v[2] | ((uint32_t)v[3] << 16);
@@ -320,15 +453,46 @@ extern "C" hipError_t arena_image_batch_resized(ArenaImageBatch a, const int* bo
   const int quads = (a.Hc / 2) * (a.Wc / 2);
   const dim3 g((unsigned)((quads + 255) / 256), (unsigned)a.B);
   if (layout == 0)
-    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 0>), g, dim3(256), 0, st, a, boxes,
-                       n_boxes, box_out);
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 0, IMAGE_PLAIN>), g, dim3(256), 0, st,
+                       a, boxes, n_boxes, box_out, ArenaImageColor{});
   else if (out_f32)
-    hipLaunchKernelGGL((image_batch_resized_kernel<float, 1>), g, dim3(256), 0, st, a, boxes,
-                       n_boxes, box_out);
+    hipLaunchKernelGGL((image_batch_resized_kernel<float, 1, IMAGE_PLAIN>), g, dim3(256), 0, st, a,
+                       boxes, n_boxes, box_out, ArenaImageColor{});
   else
-    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 1>), g, dim3(256), 0, st, a, boxes,
-                       n_boxes, box_out);
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 1, IMAGE_PLAIN>), g, dim3(256), 0, st,
+                       a, boxes, n_boxes, box_out, ArenaImageColor{});
   hipError_t e = hipGetLastError();
+  if (e != hipSuccess || !advance) return e;
+  hipLaunchKernelGGL(image_cursor_kernel, dim3(1), dim3(1), 0, st, a.cursor);
+  return hipGetLastError();
+}
+
+// The resized training batch with the colour distortion: arena_image_batch_resized's operands plus
+// `col` (abi.h). Two launches of the same grid, the channel sums and then the batch, before the
+// cursor's.
+extern "C" hipError_t arena_image_batch_color(ArenaImageBatch a, const int* boxes, int n_boxes,
+                                              int* box_out, ArenaImageColor col, int layout,
+                                              int out_f32, int advance, hipStream_t st) {
+  if (!image_batch_args_ok(a, layout, out_f32) || !a.train || n_boxes < 1 || n_boxes > 4096 ||
+      col.n_matrices < 1 || col.n_matrices > 4096 || col.k_lo < 0 || col.k_hi < col.k_lo ||
+      col.k_hi > 4096 || col.delta < 0 || col.delta > 255)
+    return hipErrorInvalidValue;
+  const int quads = (a.Hc / 2) * (a.Wc / 2);
+  const dim3 g((unsigned)((quads + 255) / 256), (unsigned)a.B);
+  hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 0, IMAGE_SUMS>), g, dim3(256), 0, st, a,
+                     boxes, n_boxes, box_out, col);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (layout == 0)
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 0, IMAGE_COLOR>), g, dim3(256), 0, st,
+                       a, boxes, n_boxes, box_out, col);
+  else if (out_f32)
+    hipLaunchKernelGGL((image_batch_resized_kernel<float, 1, IMAGE_COLOR>), g, dim3(256), 0, st, a,
+                       boxes, n_boxes, box_out, col);
+  else
+    hipLaunchKernelGGL((image_batch_resized_kernel<uint16_t, 1, IMAGE_COLOR>), g, dim3(256), 0, st,
+                       a, boxes, n_boxes, box_out, col);
+  e = hipGetLastError();
   if (e != hipSuccess || !advance) return e;
   hipLaunchKernelGGL(image_cursor_kernel, dim3(1), dim3(1), 0, st, a.cursor);
   return hipGetLastError();
