@@ -335,6 +335,7 @@ constexpr int kXsStride = 80;  // floats
 constexpr int kXItems = (kMC * 16) / 256;  // X staging items per thread (16 per row)
 constexpr int kZItems = (kMC * 4) / 256;   // dZ staging items per thread (4 float4 per row)
 constexpr int kDItems = (kMC * 16) / 256;  // head logits items per thread ([m][16])
+constexpr int kTsStride = 68;  // floats: the epilogue's transposed 16 x 64 tile (fits the Ds image)
 
 // Raw workgroup barrier for LDS hand-offs: waits only for this wave's LDS ops (lgkmcnt), NOT for
 // its outstanding global loads (__syncthreads() would emit vmcnt(0) and drain the prefetches).
@@ -364,6 +365,23 @@ __device__ __forceinline__ void load_x_items(const ArenaWGradProblem& P, const G
   }
 }
 
+// The vectorised epilogue's precondition: float4 pieces along k stay inside a row and aligned.
+__host__ __device__ inline bool wgrad_vec_ok(const ArenaWGradProblem& P) {
+  const uintptr_t a = P.mode == 1 ? ((uintptr_t)P.pW | (uintptr_t)P.mW | (uintptr_t)P.vW)
+                                  : (uintptr_t)P.gW;
+  return (P.K & 3) == 0 && (a & 15) == 0;
+}
+
+// 16-byte write-through (sc1) store for the epilogue: the bytes leave the XCD's L2 as they are
+// stored instead of staying dirty until the end-of-kernel release writes them back, which the
+// next kernel's start otherwise waits for (4.8 MB of P/M/V per MNIST step; docs/perf.md, "Adam
+// epilogue: write-through float4 stores"). The s_nop keeps hipcc's next instruction off the data
+// registers until the store has read them.
+__device__ __forceinline__ void store_f4_wt(float* p, const float4& v) {
+  const f32x4 x = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+}
+
 __device__ __forceinline__ int load_label(const ArenaRowSource& lab, long long pr) {
   if (lab.dtype == 1) return (int)static_cast<const uint8_t*>(lab.ptr)[pr];
   if (lab.dtype == 2) return static_cast<const int*>(lab.ptr)[pr];
@@ -376,7 +394,8 @@ __device__ __forceinline__ int load_label(const ArenaRowSource& lab, long long p
 // chunk is issued at once (gathered X block, dZ slice -- or the softmax head's raw logits, labels
 // and the W2/H slices dZ is derived from -- then the tile's Adam state), (2) LDS images, (3) in
 // head mode each workgroup recomputes softmax-xent for the chunk's rows (cheap, removes a kernel)
-// and derives dZ, (4) 4 waves run the MFMA K-loop over m; the Adam update is the epilogue.
+// and derives dZ, (4) 4 waves run the MFMA K-loop over m; the Adam update is the epilogue
+// (the tile transposed through LDS to one float4 along k per thread, stored write-through).
 //   A operand (dZᵀ): lane l -> Zs[m = 4s + (l>>4)][n = l&15]         (stride 16: conflict-free)
 //   B operand (X)  : lane l -> Xs[m = 4s + (l>>4)][k = 16w + (l&15)] (stride 80 ≡ 16 mod 32 banks:
 //                    the two 16-lane groups of each half-wave hit disjoint banks)
@@ -470,6 +489,13 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   f32x4 accb = {0.f, 0.f, 0.f, 0.f};
   float pw[4], mw[4], vw[4], pb[4], mb[4], vb[4];
+  // Vectorised epilogue: the 16 x 64 accumulator tile is transposed through LDS so that thread t
+  // owns the float4 dW[vn][vk .. vk+3], and P/M/V (or the gradient) move as one 16-byte access
+  // each. Needs K % 4 == 0 and 16-byte-aligned rows; the spec path has both checked by the host,
+  // anything else keeps the scalar epilogue in the MFMA D layout.
+  float4 pw4 = make_float4(0.f, 0.f, 0.f, 0.f), mw4 = pw4, vw4 = pw4;
+  const int vn = n0 + ((int)threadIdx.x >> 4), vk = k0 + 4 * ((int)threadIdx.x & 15);
+  const bool vec = WS::known || wgrad_vec_ok(P);
   // spec path: the host guarantees M <= kMC, so the chunk loop (and every mc0 == 0 test) folds away
   const int nchunks = WS::known ? 1 : (P.M + kMC - 1) / kMC;
   for (int ci = 0; ci < nchunks; ++ci) {
@@ -578,10 +604,19 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
 #pragma unroll
       for (int r = 0; r < 4; ++r) { pb[r] = 0.1f; mb[r] = 0.01f; vb[r] = 0.001f; }
     } else if (mc0 == 0 && mode == 1) {
+      if (vec) {  // this thread's float4 of the transposed tile (see the epilogue)
+        if constexpr (WS::known) {  // (the generic path loads it in the epilogue: registers)
+          const long long off = (long long)min(vn, P.N - 1) * P.K + min(vk, P.K - 4);
+          pw4 = *reinterpret_cast<const float4*>(P.pW + off);
+          mw4 = *reinterpret_cast<const float4*>(P.mW + off);
+          vw4 = *reinterpret_cast<const float4*>(P.vW + off);
+        }
+      } else {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long long off = (long long)min(n0 + 4 * g + r, P.N - 1) * P.K + kkc;
-        pw[r] = P.pW[off]; mw[r] = P.mW[off]; vw[r] = P.vW[off];
+        for (int r = 0; r < 4; ++r) {
+          const long long off = (long long)min(n0 + 4 * g + r, P.N - 1) * P.K + kkc;
+          pw[r] = P.pW[off]; mw[r] = P.mW[off]; vw[r] = P.vW[off];
+        }
       }
       {  // every wave loads (a branch around loads drains vmcnt); only the bias wave uses them
         const float* pbp = has_bias ? P.pB : P.pW;
@@ -751,11 +786,30 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
   AdamCoef co{};
   if (mode == 1) co = adam_coef_tl(args.adam, (float)adam_t, adam_lr);
 
-  if (mode == 0) {
+  float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (vec) {
+    // D layout (lane: 4 scalars in 4 rows) -> [n][k] image in Ds (its last readers, the dZ
+    // derivation, are behind the K-loop's barrier) -> one float4 along k per thread. Stride 68:
+    // the four 16-lane groups of a store land on two bank phases, float4 reads stay aligned.
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = n0 + 4 * g + r;
-      if (kk < P.K && n < P.N) P.gW[(long long)n * P.K + kk] = acc[r] * args.grad_scale;
+    for (int r = 0; r < 4; ++r) Ds[(4 * g + r) * kTsStride + 16 * w + c] = acc[r];
+    lds_barrier();
+    g4 = *reinterpret_cast<const float4*>(&Ds[((int)threadIdx.x >> 4) * kTsStride +
+                                              4 * ((int)threadIdx.x & 15)]);
+  }
+  const bool vok = vk < P.K && vn < P.N;  // K % 4 == 0: the whole float4 is inside the row
+  if (mode == 0) {
+    if (vec) {
+      if (vok)
+        store_f4_wt(P.gW + (long long)vn * P.K + vk,
+                 make_float4(g4.x * args.grad_scale, g4.y * args.grad_scale,
+                             g4.z * args.grad_scale, g4.w * args.grad_scale));
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + 4 * g + r;
+        if (kk < P.K && n < P.N) P.gW[(long long)n * P.K + kk] = acc[r] * args.grad_scale;
+      }
     }
     if (bias_wave && has_bias && c == 0) {
 #pragma unroll
@@ -765,13 +819,31 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
       }
     }
   } else {
+    if (vec) {
+      if (vok) {
+        const long long off = (long long)vn * P.K + vk;
+        if constexpr (!WS::known) {
+          pw4 = *reinterpret_cast<const float4*>(P.pW + off);
+          mw4 = *reinterpret_cast<const float4*>(P.mW + off);
+          vw4 = *reinterpret_cast<const float4*>(P.vW + off);
+        }
+        adam_apply(co, g4.x, pw4.x, mw4.x, vw4.x);
+        adam_apply(co, g4.y, pw4.y, mw4.y, vw4.y);
+        adam_apply(co, g4.z, pw4.z, mw4.z, vw4.z);
+        adam_apply(co, g4.w, pw4.w, mw4.w, vw4.w);
+        store_f4_wt(P.pW + off, pw4);
+        store_f4_wt(P.mW + off, mw4);
+        store_f4_wt(P.vW + off, vw4);
+      }
+    } else {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = n0 + 4 * g + r;
-      if (kk < P.K && n < P.N) {
-        const long long off = (long long)n * P.K + kk;
-        adam_apply(co, acc[r], pw[r], mw[r], vw[r]);
-        P.pW[off] = pw[r]; P.mW[off] = mw[r]; P.vW[off] = vw[r];
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + 4 * g + r;
+        if (kk < P.K && n < P.N) {
+          const long long off = (long long)n * P.K + kk;
+          adam_apply(co, acc[r], pw[r], mw[r], vw[r]);
+          P.pW[off] = pw[r]; P.mW[off] = mw[r]; P.vW[off] = vw[r];
+        }
       }
     }
     if (bias_wave && has_bias && c == 0) {
@@ -796,7 +868,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     WGradArgs args) {
   __shared__ __attribute__((aligned(16))) float Xs[kMC * kXsStride];
   __shared__ __attribute__((aligned(16))) float Zs[kMC * 16];
-  __shared__ __attribute__((aligned(16))) float Ds[kMC * 16];  // head: logits -> dlogits [m][c]
+  __shared__ __attribute__((aligned(16))) float Ds[kMC * 16];  // head: logits -> dlogits [m][c];
+                                                               // then the epilogue's transposed tile
   __shared__ __attribute__((aligned(16))) float W2s[16 * 16];  // head: W2 slice [c][n]
   __shared__ int Ys[kMC];                                      // head: labels
   __shared__ float B2s[16];
@@ -1439,7 +1512,8 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
                         probs[1].xt == 0 && probs[1].hd_mode == 1 && probs[1].x.idx == nullptr &&
                         probs[0].mode == probs[1].mode && probs[0].M <= kMC &&
                         (probs[0].mode == 0 || (adam.t_ptr && adam.lr_ptr)) && head.step &&
-                        probs[1].M <= kMC && head.lab.dtype == (g0 ? 1 : 2);
+                        probs[1].M <= kMC && head.lab.dtype == (g0 ? 1 : 2) &&
+                        wgrad_vec_ok(probs[0]) && wgrad_vec_ok(probs[1]);
   const dim3 grid(blocks), block(256);
   if (mlp_pair) {
     const int m = probs[0].mode & 1;
