@@ -7,7 +7,8 @@ This is the same workload, built for MI355X:
 
 * ResNet v1.5 (``arena_amd.models.resnet``), NHWC (``channels_last``), bf16 autocast on the MFMA
   conv/GEMM paths, fp32 master weights;
-* momentum SGD with weight decay, as in tf_cnn_benchmarks;
+* momentum SGD with weight decay, as in tf_cnn_benchmarks; ``--optimizer`` selects its plain
+  SGD, RMSProp or Adam instead (TF1's forms; fused master-weight kernels on one rank);
 * one process per GPU: ``hvd.DistributedOptimizer`` buckets (RCCL or the xGMI kernel on a comm
   stream) overlap the gradient allreduce with backward;
 * output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``;
@@ -86,6 +87,18 @@ def parse(argv=None):
     ap.add_argument("--minimum_learning_rate", type=float, default=0.0,
                     help="lower bound of the exponential staircase")
     ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--optimizer", choices=["momentum", "sgd", "rmsprop", "adam"],
+                    default="momentum",
+                    help="tf_cnn_benchmarks' flag: momentum SGD, plain SGD (momentum 0), or TF1's "
+                         "RMSProp / Adam; with master weights on one rank the fused multi-tensor "
+                         "kernels inside the captured step, else plain tensor ops")
+    ap.add_argument("--rmsprop_decay", type=float, default=None, help="default 0.9")
+    ap.add_argument("--rmsprop_momentum", type=float, default=None, help="default 0.9")
+    ap.add_argument("--rmsprop_epsilon", type=float, default=None,
+                    help="default 1.0 (inside the square root, as in TF1)")
+    ap.add_argument("--adam_beta1", type=float, default=None, help="default 0.9")
+    ap.add_argument("--adam_beta2", type=float, default=None, help="default 0.999")
+    ap.add_argument("--adam_epsilon", type=float, default=None, help="default 1e-8")
     ap.add_argument("--weight_decay", type=float, default=4e-5)
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--data_format", choices=["NHWC", "NCHW"], default="NHWC")
@@ -184,7 +197,26 @@ def parse(argv=None):
         ap.error("--num_learning_rate_warmup_epochs must be >= 0")
     if has_schedule(args) and args.eval:
         ap.error("the learning-rate flags do not apply to --eval")
+    for family, defaults in OPTIMIZER_FLAGS.items():
+        given = [f for f in defaults if getattr(args, f) is not None]
+        if given and args.optimizer != family:
+            ap.error(f"--{given[0]} needs --optimizer {family}")
+        for f, default in defaults.items():
+            v = default if getattr(args, f) is None else getattr(args, f)
+            if f.endswith("epsilon"):
+                if not v > 0.0:
+                    ap.error(f"--{f} must be > 0")
+            elif not 0.0 <= v < 1.0:
+                ap.error(f"--{f} must lie in [0, 1)")
+            setattr(args, f, v)
     return args
+
+
+# the flags that belong to one --optimizer each, with tf_cnn_benchmarks' defaults
+OPTIMIZER_FLAGS = {
+    "rmsprop": {"rmsprop_decay": 0.9, "rmsprop_momentum": 0.9, "rmsprop_epsilon": 1.0},
+    "adam": {"adam_beta1": 0.9, "adam_beta2": 0.999, "adam_epsilon": 1e-8},
+}
 
 
 IMAGENET_TRAIN_IMAGES = 1281167    # tf_cnn_benchmarks' epoch when no dataset defines one
@@ -302,11 +334,19 @@ def build(args, dev, world, segments=None):
     ``DeviceLR`` (``schedule_of(opt)``) in every update kernel; the other paths keep their float
     ``lr`` and the caller sets it on the host each step."""
     from ..parallel import hvd
+    mw = getattr(args, "master_weights", "auto")
+    name = getattr(args, "optimizer", "momentum")
+    momentum = 0.0 if name == "sgd" else args.momentum
+    if name in ("rmsprop", "adam") and world > 1:
+        if mw == "on":
+            raise SystemExit(f"--optimizer {name} --master_weights on: the sharded xGMI / RCCL "
+                             "update of data-parallel master weights (ShardedMasterSGD) implements "
+                             "momentum SGD only; use --master_weights off")
+        mw = "off"
     model = build_model(args, dev)
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         (no_decay if p.ndim <= 1 else decay).append(p)   # no decay on BN / bias
-    mw = getattr(args, "master_weights", "auto")
     master = mw == "on" or (
         mw == "auto" and dev.type == "cuda"
         and getattr(args, "dtype", "bf16") == "bf16" and all(p.numel() % 4 == 0 for p in decay))
@@ -328,33 +368,35 @@ def build(args, dev, world, segments=None):
         opt = ShardedMasterSGD(
             [{"params": decay, "weight_decay": args.weight_decay},
              {"params": no_decay, "weight_decay": 0.0, "weights": "fp32"}],
-            lr=lr, momentum=args.momentum, bucket_mb=args.bucket_mb,
+            lr=lr, momentum=momentum, bucket_mb=args.bucket_mb,
             backend=comm, order=list(model.parameters()))
         if hvd.rank() == 0 and opt.backend != "xgmi" and comm == "auto":
             print(f"[rank 0] ShardedMasterSGD over RCCL, {opt.backend} (ranks cannot map each "
                   "other's GPUs)", file=sys.stderr, flush=True)
     if opt is not None:
         pass                   # data parallel, sharded
+    elif name in ("rmsprop", "adam"):
+        opt = build_rmsprop_or_adam(args, name, decay, no_decay, lr if master else None)
     elif master and sched is not None:
         # as below, with the BN / bias group on the multi-tensor kernel that reads the device lr
         from ..ops.optim import MasterSGD, MultiTensorSGD32, OptimizerGroup
         opt = OptimizerGroup(
-            MasterSGD(decay, lr=sched, momentum=args.momentum, weight_decay=args.weight_decay),
-            MultiTensorSGD32(no_decay, lr=sched, momentum=args.momentum))
+            MasterSGD(decay, lr=sched, momentum=momentum, weight_decay=args.weight_decay),
+            MultiTensorSGD32(no_decay, lr=sched, momentum=momentum))
     elif master:
         # conv/fc weights live in bf16 (fp32 masters inside MasterSGD): no per-step casts
         from ..ops.optim import MasterSGD, OptimizerGroup
         opt = OptimizerGroup(
-            MasterSGD(decay, lr=args.learning_rate, momentum=args.momentum,
+            MasterSGD(decay, lr=args.learning_rate, momentum=momentum,
                       weight_decay=args.weight_decay),
             # BN scales / shifts and biases (fp32): torch's fused multi-tensor SGD, one launch
             # instead of the five of the foreach form
-            torch.optim.SGD(no_decay, lr=args.learning_rate, momentum=args.momentum,
+            torch.optim.SGD(no_decay, lr=args.learning_rate, momentum=momentum,
                             fused=dev.type == "cuda", foreach=None if dev.type == "cuda" else True))
     else:
         opt = torch.optim.SGD([{"params": decay, "weight_decay": args.weight_decay},
                                {"params": no_decay, "weight_decay": 0.0}],
-                              lr=args.learning_rate, momentum=args.momentum,
+                              lr=args.learning_rate, momentum=momentum,
                               foreach=dev.type == "cuda")
     if world > 1 and not master:
         opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
@@ -364,11 +406,34 @@ def build(args, dev, world, segments=None):
     return model, opt, x, y
 
 
+def build_rmsprop_or_adam(args, name, decay, no_decay, master_lr):
+    """``--optimizer rmsprop`` / ``adam``. ``master_lr`` (a float or a ``DeviceLR``): the fused
+    master-weight pair, the decayed weights in bf16 with fp32 masters and the BN / bias group in
+    fp32, both on the multi-tensor kernels (Adam: one shared clock, ticked by the first). None:
+    the same formulas in plain tensor ops over fp32 parameters (``TFRMSprop`` / ``TFAdam``)."""
+    from ..ops import optim
+    if name == "rmsprop":
+        hyper = {"decay": args.rmsprop_decay, "momentum": args.rmsprop_momentum,
+                 "eps": args.rmsprop_epsilon}
+        fused_pair, plain = (optim.MasterRMSprop, optim.MultiTensorRMSprop32), optim.TFRMSprop
+    else:
+        hyper = {"betas": (args.adam_beta1, args.adam_beta2), "eps": args.adam_epsilon}
+        fused_pair, plain = (optim.MasterAdam, optim.MultiTensorAdam32), optim.TFAdam
+    if master_lr is None:
+        return plain([{"params": decay, "weight_decay": args.weight_decay},
+                      {"params": no_decay, "weight_decay": 0.0}], lr=args.learning_rate, **hyper)
+    first = fused_pair[0](decay, lr=master_lr, weight_decay=args.weight_decay, **hyper)
+    if name == "adam":
+        hyper["clock"] = first.clock
+    return optim.OptimizerGroup(first, fused_pair[1](no_decay, lr=master_lr, **hyper))
+
+
 def schedule_of(opt):
     """The ``DeviceLR`` an optimizer's update kernels read (None: float learning rates)."""
     from ..ops.schedule import DeviceLR
     for o in getattr(opt, "opts", (opt,)):
-        for name in ("lr_sched", "lr"):        # ShardedMasterSGD / MasterSGD, MultiTensorSGD32
+        # ShardedMasterSGD / every flat-buffer optimizer of ops.optim (SGD, RMSProp, Adam)
+        for name in ("lr_sched", "lr"):
             s = getattr(o, name, None)
             if isinstance(s, DeviceLR):
                 return s
@@ -460,7 +525,10 @@ def main(argv=None) -> int:
     world, rank = hvd.size(), hvd.rank()
     if dev.type == "cuda":
         torch.cuda.set_device(dev)
-        torch.backends.cudnn.benchmark = True      # MIOpen: pick the fastest conv solvers once
+        # MIOpen: pick the fastest conv solvers once. The pick is timed, so it can differ from
+        # process to process; ARENA_MIOPEN_BENCHMARK=0 leaves the library its untimed choice
+        # (for comparing two runs exactly)
+        torch.backends.cudnn.benchmark = os.environ.get("ARENA_MIOPEN_BENCHMARK", "1") == "1"
     else:
         share_cpu_threads(int(os.environ.get("LOCAL_WORLD_SIZE", world)))
     amp = torch.bfloat16 if args.dtype == "bf16" else None
@@ -621,7 +689,7 @@ def main(argv=None) -> int:
             res = {"model": args.model, "images_per_s": round(total, 2),
                    "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
                    "batch_per_device": args.batch_size, "devices": world,
-                   "dtype": args.dtype, "comm": comm_name(opt),
+                   "dtype": args.dtype, "comm": comm_name(opt), "optimizer": args.optimizer,
                    "exec": "hipgraph" if graph is not None else "eager",
                    "final_loss": round(float(loss), 4)}
             if counts is not None:

@@ -181,3 +181,76 @@ def lr_schedule(table: Tensor, step: Tensor, lr: Tensor) -> None:
     """``lr[0] = schedule(step[0])``, then ``step[0] += 1``, in one launch (``table``: the segment
     table of :func:`arena_amd.ops.schedule.encode`)."""
     _impl(lr).lr_schedule(table, step, lr)
+
+
+def _one_minus(x: float) -> float:
+    """``1 - x`` in fp64 (the kernels receive it rounded once to fp32: the fp32 difference
+    ``1 - float32(0.999)`` is 4.7e-5 off in relative terms)."""
+    return 1.0 - float(x)
+
+
+def mt_rmsprop_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tensor, ms: Tensor,
+                      mom: Tensor, wbf: Tensor, *, lr: float, decay: float = 0.9,
+                      momentum: float = 0.9, eps: float = 1.0, weight_decay: float = 0.0,
+                      lr_t: Optional[Tensor] = None) -> None:
+    """TF1 RMSProp over bf16 grads with fp32 masters, one launch per 48 tensors (the layout of
+    :func:`mt_sgd_master` with two state buffers): d = g + wd * w; ms = decay * ms + (1 - decay)
+    * d * d; mom = momentum * mom + lr * d / sqrt(ms + eps); w -= mom; ``wbf`` gets the rounded
+    bf16 weights. Semantics: :mod:`arena_amd.ops.reference`."""
+    _impl(master).mt_rmsprop_master(list(grads), [int(o) for o in offsets], master, ms, mom, wbf,
+                                    float(lr), float(decay), _one_minus(decay), float(momentum),
+                                    float(eps), float(weight_decay),
+                                    lr_t=_check_lr_t(lr_t, master))
+
+
+def mt_rmsprop_f32(grads: Sequence[Tensor], offsets: Sequence[int], w: Tensor, ms: Tensor,
+                   mom: Tensor, *, lr: float, decay: float = 0.9, momentum: float = 0.9,
+                   eps: float = 1.0, weight_decay: float = 0.0, scale: float = 1.0,
+                   lr_t: Optional[Tensor] = None) -> None:
+    """TF1 RMSProp over fp32 tensors with fp32 gradients (any sizes and offsets, as
+    :func:`mt_sgd_f32`); d = g * scale + wd * w."""
+    _impl(w).mt_rmsprop_f32(list(grads), [int(o) for o in offsets], w, ms, mom, float(lr),
+                            float(decay), _one_minus(decay), float(momentum), float(eps),
+                            float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w))
+
+
+def _check_corr(corr: Tensor, like: Tensor) -> Tensor:
+    """The Adam clock's bias correction is one fp32 value on the updated tensors' device."""
+    if corr.dtype != torch.float32 or corr.numel() != 1 or corr.device != like.device:
+        raise ValueError(f"corr must be a float32 [1] tensor on {like.device} (got {corr.dtype} "
+                         f"{tuple(corr.shape)} on {corr.device})")
+    return corr
+
+
+def mt_adam_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tensor, m: Tensor,
+                   v: Tensor, wbf: Tensor, corr: Tensor, *, lr: float, betas=(0.9, 0.999),
+                   eps: float = 1e-8, weight_decay: float = 0.0,
+                   lr_t: Optional[Tensor] = None) -> None:
+    """TF1 Adam over bf16 grads with fp32 masters, one launch per 48 tensors: d = g + wd * w;
+    m = b1 * m + (1 - b1) * d; v = b2 * v + (1 - b2) * d * d; w -= (lr * corr) * m / (sqrt(v) +
+    eps); ``wbf`` gets the rounded bf16 weights. ``corr`` (fp32 [1]) is the bias correction of
+    this step, kept on the device by :func:`adam_tick`."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    _impl(master).mt_adam_master(list(grads), [int(o) for o in offsets], master, m, v, wbf,
+                                 _check_corr(corr, master), float(lr), b1, _one_minus(b1), b2,
+                                 _one_minus(b2), float(eps), float(weight_decay),
+                                 lr_t=_check_lr_t(lr_t, master))
+
+
+def mt_adam_f32(grads: Sequence[Tensor], offsets: Sequence[int], w: Tensor, m: Tensor, v: Tensor,
+                corr: Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                weight_decay: float = 0.0, scale: float = 1.0,
+                lr_t: Optional[Tensor] = None) -> None:
+    """TF1 Adam over fp32 tensors with fp32 gradients (any sizes and offsets, as
+    :func:`mt_sgd_f32`); d = g * scale + wd * w."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    _impl(w).mt_adam_f32(list(grads), [int(o) for o in offsets], w, m, v, _check_corr(corr, w),
+                         float(lr), b1, _one_minus(b1), b2, _one_minus(b2), float(eps),
+                         float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w))
+
+
+def adam_tick(step: Tensor, pow: Tensor, corr: Tensor, b1: float, b2: float) -> None:
+    """One tick of Adam's device clock, in one launch: ``pow *= (b1, b2)`` (fp64 running products
+    ``b1^t``, ``b2^t``), ``corr[0] = float32(sqrt(1 - pow[1]) / (1 - pow[0]))``, ``step[0] += 1``
+    (:func:`arena_amd.ops.reference.reference_adam_corr`)."""
+    _impl(corr).adam_tick(step, pow, corr, float(b1), float(b2))

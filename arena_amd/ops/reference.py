@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 _M32 = 0xFFFFFFFF
@@ -298,6 +299,113 @@ def mt_sgd_f32(grads, offsets, w, mom, lr, momentum, weight_decay, scale, lr_t=N
         d = _storage_flat(g) * scale + weight_decay * ws
         m.mul_(momentum).add_(d)
         ws.sub_(lr * m)
+
+
+# ------------------------------------------------------------------------------------------------
+# RMSProp and Adam, TF1's forms (tf_cnn_benchmarks' defaults assume them: --rmsprop_epsilon 1.0
+# sits inside the square root). Defined once, here; the HIP kernels (``mt_opt_*_kernel`` in
+# csrc/ops/mlp_kernels.hip), ``TFRMSprop`` / ``TFAdam`` and the tests follow it. Both take the
+# coupled gradient of the SGD kernels, ``d = g * scale + wd * w`` (``scale`` only on the fp32
+# group), and every operation below is an fp32 operation in the order written:
+#
+#   RMSProp (non-centred; ms starts at 1.0 as TF's slot does, mom at 0):
+#       ms  = rho * ms + omr * (d * d)
+#       mom = mu * mom + lr * d / sqrt(ms + eps)
+#       w   = w - mom
+#   Adam (m and v start at 0):
+#       m = b1 * m + omb1 * d
+#       v = b2 * v + omb2 * (d * d)
+#       w = w - (lr * corr) * m / (sqrt(v) + eps)
+#
+# ``omr = 1 - rho``, ``omb1 = 1 - b1`` and ``omb2 = 1 - b2`` are formed by the caller in fp64 and
+# rounded to fp32 once (``1 - float32(0.999)`` is 4.7e-5 off in relative terms). ``corr`` is the
+# bias correction ``sqrt(1 - b2^t) / (1 - b1^t)`` of step t = 1, 2, ...:
+# :func:`reference_adam_corr`, kept on the device by the ``arena_adam_tick`` kernel
+# (:func:`adam_tick` here).
+# ------------------------------------------------------------------------------------------------
+def reference_adam_corr(b1: float, b2: float, t: int) -> np.float32:
+    """Adam's bias correction at step ``t`` >= 1 (the definition ``arena_adam_tick`` matches bit
+    for bit): ``b1^t`` and ``b2^t`` as running products of Python floats (fp64, one rounding per
+    operation), ``float32(sqrt(1 - b2^t) / (1 - b1^t))``."""
+    t = int(t)
+    if t < 1:
+        raise ValueError(f"Adam's bias correction is defined from step 1 on, got t = {t}")
+    b1, b2 = float(b1), float(b2)
+    p1 = p2 = 1.0
+    for _ in range(t):
+        p1 *= b1
+        p2 *= b2
+    return np.float32(math.sqrt(1.0 - p2) / (1.0 - p1))
+
+
+def adam_tick(step, pow, corr, b1, b2):
+    """CPU form of the ``arena_adam_tick`` kernel: one step of the running products."""
+    p1 = float(pow[0].item()) * float(b1)
+    p2 = float(pow[1].item()) * float(b2)
+    pow[0], pow[1] = p1, p2
+    corr.fill_(float(np.float32(math.sqrt(1.0 - p2) / (1.0 - p1))))
+    step.add_(1)
+
+
+def _f32(v) -> torch.Tensor:
+    """A Python number rounded once to fp32, as the kernels receive their arguments."""
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def _rmsprop(g, w, ms, mom, lr, rho, omr, mu, eps, wd, scale):
+    d = g * _f32(scale) + _f32(wd) * w
+    ms.copy_(_f32(rho) * ms + _f32(omr) * (d * d))
+    mom.copy_(_f32(mu) * mom + _f32(lr) * d / torch.sqrt(ms + _f32(eps)))
+    w.sub_(mom)
+
+
+def _adam(g, w, m, v, step, b1, omb1, b2, omb2, eps, wd, scale):
+    d = g * _f32(scale) + _f32(wd) * w
+    m.copy_(_f32(b1) * m + _f32(omb1) * d)
+    v.copy_(_f32(b2) * v + _f32(omb2) * (d * d))
+    w.sub_(step * m / (torch.sqrt(v) + _f32(eps)))
+
+
+def mt_rmsprop_master(grads, offsets, master, ms, mom, wbf, lr, rho, omr, momentum, eps,
+                      weight_decay, lr_t=None):
+    """CPU reference of the HIP ``mt_rmsprop_master`` kernel."""
+    lr = _lr_value(lr, lr_t)
+    for g, off in zip(grads, offsets):
+        s = slice(off, off + g.numel())
+        _rmsprop(_storage_flat(g).float(), master[s], ms[s], mom[s], lr, rho, omr, momentum, eps,
+                 weight_decay, 1.0)
+        wbf[s].copy_(master[s])
+
+
+def mt_rmsprop_f32(grads, offsets, w, ms, mom, lr, rho, omr, momentum, eps, weight_decay, scale,
+                   lr_t=None):
+    """CPU reference of the HIP ``mt_rmsprop_f32`` kernel."""
+    lr = _lr_value(lr, lr_t)
+    for g, off in zip(grads, offsets):
+        s = slice(off, off + g.numel())
+        _rmsprop(_storage_flat(g), w[s], ms[s], mom[s], lr, rho, omr, momentum, eps, weight_decay,
+                 scale)
+
+
+def mt_adam_master(grads, offsets, master, m, v, wbf, corr, lr, b1, omb1, b2, omb2, eps,
+                   weight_decay, lr_t=None):
+    """CPU reference of the HIP ``mt_adam_master`` kernel (``corr``: the clock's fp32 [1])."""
+    step = _f32(_lr_value(lr, lr_t)) * corr.reshape(())
+    for g, off in zip(grads, offsets):
+        s = slice(off, off + g.numel())
+        _adam(_storage_flat(g).float(), master[s], m[s], v[s], step, b1, omb1, b2, omb2, eps,
+              weight_decay, 1.0)
+        wbf[s].copy_(master[s])
+
+
+def mt_adam_f32(grads, offsets, w, m, v, corr, lr, b1, omb1, b2, omb2, eps, weight_decay, scale,
+                lr_t=None):
+    """CPU reference of the HIP ``mt_adam_f32`` kernel."""
+    step = _f32(_lr_value(lr, lr_t)) * corr.reshape(())
+    for g, off in zip(grads, offsets):
+        s = slice(off, off + g.numel())
+        _adam(_storage_flat(g), w[s], m[s], v[s], step, b1, omb1, b2, omb2, eps, weight_decay,
+              scale)
 
 
 def lr_schedule(table, step, lr):

@@ -255,6 +255,31 @@ hipError_t arena_mt_sgd_f32(const float* const* grads, const long long* offs, co
 // fp64 values as int64 bit patterns) at *step, then *step += 1.
 hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
                              hipStream_t stream);
+// RMSProp / Adam (TF1 forms, arena_amd/ops/reference.py) as multi-tensor updates. *_master: bf16
+// gradients, fp32 masters and two fp32 state buffers, rounded bf16 weights to wbf (offs / ns
+// multiples of 4); *_f32: fp32 tensors and gradients, any sizes. omr / omb1 / omb2 are 1 - rho /
+// 1 - b1 / 1 - b2 formed in fp64 by the caller; corr is arena_adam_tick's bias correction.
+hipError_t arena_mt_rmsprop_master(const void* const* grads, const long long* offs,
+                                   const long long* ns, int count, float* master, float* ms,
+                                   float* mom, void* wbf, float lr, const float* lr_ptr, float rho,
+                                   float omr, float mu, float eps, float wd, hipStream_t stream);
+hipError_t arena_mt_adam_master(const void* const* grads, const long long* offs,
+                                const long long* ns, int count, float* master, float* m, float* v,
+                                void* wbf, float lr, const float* lr_ptr, const float* corr,
+                                float b1, float omb1, float b2, float omb2, float eps, float wd,
+                                hipStream_t stream);
+hipError_t arena_mt_rmsprop_f32(const float* const* grads, const long long* offs,
+                                const long long* ns, int count, float* w, float* ms, float* mom,
+                                float lr, const float* lr_ptr, float rho, float omr, float mu,
+                                float eps, float wd, float scale, hipStream_t stream);
+hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, const long long* ns,
+                             int count, float* w, float* m, float* v, float lr,
+                             const float* lr_ptr, const float* corr, float b1, float omb1, float b2,
+                             float omb2, float eps, float wd, float scale, hipStream_t stream);
+// t = *step + 1; pw[0] *= b1; pw[1] *= b2; *corr = float(sqrt(1 - pw[1]) / (1 - pw[0])) in fp64,
+// every operation rounded on its own; *step = t.
+hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,
+                           hipStream_t stream);
 #ifdef ARENA_TIMELINE
 hipError_t arena_timeline_read(long long* host, int clear);
 #endif

@@ -588,6 +588,160 @@ void lr_schedule(Tensor seg, Tensor step, Tensor lr) {
             "lr_schedule");
 }
 
+// ---- RMSProp / Adam multi-tensor updates: the argument checks of mt_sgd_master / mt_sgd_f32 ----
+struct MtSegments {
+  std::vector<const void*> ptrs;
+  std::vector<long long> offs, ns;
+};
+
+// master / st0 / st1 fp32 and wbf bf16, equal sizes on one GPU; bf16 gradients there, dense,
+// 8-byte aligned, sizes and offsets multiples of 4, inside the buffers.
+MtSegments master_segments(const std::vector<Tensor>& grads, const std::vector<int64_t>& offsets,
+                           const Tensor& master, const Tensor& st0, const Tensor& st1,
+                           const Tensor& wbf, const char* what) {
+  check_f32(master, "master");
+  check_f32(st0, "state 0");
+  check_f32(st1, "state 1");
+  check_dev(wbf, "wbf");
+  TORCH_CHECK(wbf.scalar_type() == torch::kBFloat16 && st0.numel() == master.numel() &&
+                  st1.numel() == master.numel() && wbf.numel() == master.numel(),
+              what, ": flat buffers must be fp32/fp32/fp32/bf16 of equal size");
+  TORCH_CHECK(st0.device() == master.device() && st1.device() == master.device() &&
+                  wbf.device() == master.device(),
+              what, ": flat buffers must share one GPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(st0.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(st1.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wbf.data_ptr()) % 8 == 0,
+              what, ": flat buffers must be 16-byte (wbf: 8-byte) aligned");
+  TORCH_CHECK(grads.size() == offsets.size(), what, ": offsets length");
+  MtSegments s;
+  for (size_t i = 0; i < grads.size(); ++i) {
+    const Tensor& g = grads[i];
+    TORCH_CHECK(g.is_cuda() && g.device() == master.device(), what, ": grad ", i,
+                " must be on the master buffer's GPU");
+    TORCH_CHECK(g.scalar_type() == torch::kBFloat16 && g.is_non_overlapping_and_dense(), what,
+                ": grad ", i, " must be dense bf16");
+    TORCH_CHECK(g.numel() % 4 == 0 && offsets[i] % 4 == 0 && offsets[i] >= 0 &&
+                    offsets[i] + g.numel() <= master.numel(),
+                what, ": segment ", i, " misaligned or out of bounds");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 8 == 0, what, ": grad ", i,
+                " not 8B aligned");
+    s.ptrs.push_back(g.data_ptr());
+    s.offs.push_back(offsets[i]);
+    s.ns.push_back(g.numel());
+  }
+  return s;
+}
+
+// w / st0 / st1 fp32, equal sizes, 16-byte aligned, on one GPU; dense fp32 gradients there, any
+// sizes and offsets inside the buffers.
+MtSegments f32_segments(const std::vector<Tensor>& grads, const std::vector<int64_t>& offsets,
+                        const Tensor& w, const Tensor& st0, const Tensor& st1, const char* what) {
+  check_f32(w, "w");
+  check_f32(st0, "state 0");
+  check_f32(st1, "state 1");
+  TORCH_CHECK(st0.numel() == w.numel() && st1.numel() == w.numel() &&
+                  st0.device() == w.device() && st1.device() == w.device(),
+              what, ": w and the state buffers must be equal-size buffers on one GPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(st0.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(st1.data_ptr()) % 16 == 0,
+              what, ": w and the state buffers must be 16-byte aligned");
+  TORCH_CHECK(grads.size() == offsets.size(), what, ": offsets length");
+  MtSegments s;
+  for (size_t i = 0; i < grads.size(); ++i) {
+    const Tensor& g = grads[i];
+    TORCH_CHECK(g.is_cuda() && g.device() == w.device(), what, ": grad ", i,
+                " must be on w's GPU");
+    TORCH_CHECK(g.scalar_type() == torch::kFloat32 && g.is_non_overlapping_and_dense(), what,
+                ": grad ", i, " must be dense fp32");
+    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + g.numel() <= w.numel(), what, ": segment ", i,
+                " out of bounds");
+    s.ptrs.push_back(g.data_ptr<float>());
+    s.offs.push_back(offsets[i]);
+    s.ns.push_back(g.numel());
+  }
+  return s;
+}
+
+// The Adam clock's bias correction: one fp32 value on the updated tensors' GPU.
+const float* corr_ptr(const Tensor& corr, const Tensor& like, const char* what) {
+  check_f32(corr, "corr");
+  TORCH_CHECK(corr.numel() == 1 && corr.device() == like.device(), what,
+              ": corr must hold one float32 value on the updated tensors' GPU");
+  return corr.data_ptr<float>();
+}
+
+void mt_rmsprop_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
+                       Tensor ms, Tensor mom, Tensor wbf, double lr, double rho, double omr,
+                       double momentum, double eps, double weight_decay, OptT lr_t) {
+  const MtSegments s = master_segments(grads, offsets, master, ms, mom, wbf, "mt_rmsprop_master");
+  const float* lp = opt_lr_ptr(lr_t, master, "mt_rmsprop_master");
+  check_hip(arena_mt_rmsprop_master(s.ptrs.data(), s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
+                                    master.data_ptr<float>(), ms.data_ptr<float>(),
+                                    mom.data_ptr<float>(), wbf.data_ptr(), (float)lr, lp,
+                                    (float)rho, (float)omr, (float)momentum, (float)eps,
+                                    (float)weight_decay, cur_stream()),
+            "mt_rmsprop_master");
+}
+
+void mt_adam_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
+                    Tensor m, Tensor v, Tensor wbf, Tensor corr, double lr, double b1, double omb1,
+                    double b2, double omb2, double eps, double weight_decay, OptT lr_t) {
+  const MtSegments s = master_segments(grads, offsets, master, m, v, wbf, "mt_adam_master");
+  const float* lp = opt_lr_ptr(lr_t, master, "mt_adam_master");
+  const float* cp = corr_ptr(corr, master, "mt_adam_master");
+  check_hip(arena_mt_adam_master(s.ptrs.data(), s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
+                                 master.data_ptr<float>(), m.data_ptr<float>(),
+                                 v.data_ptr<float>(), wbf.data_ptr(), (float)lr, lp, cp, (float)b1,
+                                 (float)omb1, (float)b2, (float)omb2, (float)eps,
+                                 (float)weight_decay, cur_stream()),
+            "mt_adam_master");
+}
+
+void mt_rmsprop_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor ms,
+                    Tensor mom, double lr, double rho, double omr, double momentum, double eps,
+                    double weight_decay, double scale, OptT lr_t) {
+  const MtSegments s = f32_segments(grads, offsets, w, ms, mom, "mt_rmsprop_f32");
+  const float* lp = opt_lr_ptr(lr_t, w, "mt_rmsprop_f32");
+  check_hip(arena_mt_rmsprop_f32(reinterpret_cast<const float* const*>(s.ptrs.data()),
+                                 s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
+                                 w.data_ptr<float>(), ms.data_ptr<float>(), mom.data_ptr<float>(),
+                                 (float)lr, lp, (float)rho, (float)omr, (float)momentum,
+                                 (float)eps, (float)weight_decay, (float)scale, cur_stream()),
+            "mt_rmsprop_f32");
+}
+
+void mt_adam_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor m,
+                 Tensor v, Tensor corr, double lr, double b1, double omb1, double b2, double omb2,
+                 double eps, double weight_decay, double scale, OptT lr_t) {
+  const MtSegments s = f32_segments(grads, offsets, w, m, v, "mt_adam_f32");
+  const float* lp = opt_lr_ptr(lr_t, w, "mt_adam_f32");
+  const float* cp = corr_ptr(corr, w, "mt_adam_f32");
+  check_hip(arena_mt_adam_f32(reinterpret_cast<const float* const*>(s.ptrs.data()), s.offs.data(),
+                              s.ns.data(), (int)s.ptrs.size(), w.data_ptr<float>(),
+                              m.data_ptr<float>(), v.data_ptr<float>(), (float)lr, lp, cp,
+                              (float)b1, (float)omb1, (float)b2, (float)omb2, (float)eps,
+                              (float)weight_decay, (float)scale, cur_stream()),
+            "mt_adam_f32");
+}
+
+// The Adam clock's tick: step int64 [1], pow float64 [2] (b1^t, b2^t), corr float32 [1].
+void adam_tick(Tensor step, Tensor pow, Tensor corr, double b1, double b2) {
+  check_dev(step, "step");
+  check_dev(pow, "pow");
+  check_f32(corr, "corr");
+  TORCH_CHECK(step.scalar_type() == torch::kInt64 && step.numel() == 1 &&
+                  pow.scalar_type() == torch::kFloat64 && pow.numel() == 2 && corr.numel() == 1,
+              "adam_tick: step must be int64 [1], pow float64 [2] and corr float32 [1]");
+  TORCH_CHECK(step.device() == corr.device() && pow.device() == corr.device(),
+              "adam_tick: step, pow and corr must share one GPU");
+  check_hip(arena_adam_tick(reinterpret_cast<long long*>(step.data_ptr<int64_t>()),
+                            pow.data_ptr<double>(), corr.data_ptr<float>(), b1, b2, cur_stream()),
+            "adam_tick");
+}
+
 void shard_sgd(Tensor grad, Tensor w32, Tensor mom, c10::optional<Tensor> wbf, double lr,
                double momentum, double weight_decay, double scale, OptT lr_t) {
   check_f32(w32, "w32");
@@ -2174,6 +2328,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mom"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
         py::arg("scale"), py::arg("lr_t") = py::none());
   m.def("lr_schedule", &lr_schedule);
+  m.def("mt_rmsprop_master", &mt_rmsprop_master, py::arg("grads"), py::arg("offsets"),
+        py::arg("master"), py::arg("ms"), py::arg("mom"), py::arg("wbf"), py::arg("lr"),
+        py::arg("rho"), py::arg("omr"), py::arg("momentum"), py::arg("eps"),
+        py::arg("weight_decay"), py::arg("lr_t") = py::none());
+  m.def("mt_adam_master", &mt_adam_master, py::arg("grads"), py::arg("offsets"),
+        py::arg("master"), py::arg("m"), py::arg("v"), py::arg("wbf"), py::arg("corr"),
+        py::arg("lr"), py::arg("b1"), py::arg("omb1"), py::arg("b2"), py::arg("omb2"),
+        py::arg("eps"), py::arg("weight_decay"), py::arg("lr_t") = py::none());
+  m.def("mt_rmsprop_f32", &mt_rmsprop_f32, py::arg("grads"), py::arg("offsets"), py::arg("w"),
+        py::arg("ms"), py::arg("mom"), py::arg("lr"), py::arg("rho"), py::arg("omr"),
+        py::arg("momentum"), py::arg("eps"), py::arg("weight_decay"), py::arg("scale"),
+        py::arg("lr_t") = py::none());
+  m.def("mt_adam_f32", &mt_adam_f32, py::arg("grads"), py::arg("offsets"), py::arg("w"),
+        py::arg("m"), py::arg("v"), py::arg("corr"), py::arg("lr"), py::arg("b1"),
+        py::arg("omb1"), py::arg("b2"), py::arg("omb2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("scale"), py::arg("lr_t") = py::none());
+  m.def("adam_tick", &adam_tick);
   m.def("shard_sgd", &shard_sgd, py::arg("grad"), py::arg("w32"), py::arg("mom"),
         py::arg("wbf") = py::none(), py::arg("lr"), py::arg("momentum"),
         py::arg("weight_decay"), py::arg("scale"), py::arg("lr_t") = py::none());

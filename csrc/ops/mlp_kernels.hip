@@ -1390,6 +1390,202 @@ __global__ void lr_schedule_kernel(const long long* __restrict__ seg, int n_seg,
   *step = t + 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// RMSProp and Adam in TF1's forms (arena_amd/ops/reference.py defines them) over the same MtArgs
+// walk and access pattern as the SGD kernels above. Both start from the coupled gradient
+// d = g * scale + wd * w (scale is 1 on the master path) and keep two fp32 state buffers:
+//   RMSProp (s0 = ms, s1 = mom):  ms = rho * ms + omr * (d * d)
+//                                 mom = mu * mom + lr * d / sqrt(ms + eps);  w = w - mom
+//   Adam    (s0 = m,  s1 = v):    m = b1 * m + omb1 * d;  v = b2 * v + omb2 * (d * d)
+//                                 w = w - (lr * corr) * m / (sqrt(v) + eps)
+// omr / omb1 / omb2 are 1 - rho / 1 - b1 / 1 - b2 formed by the host in fp64: the fp32 difference
+// 1 - float(0.999) is 4.7e-5 off. corr is the bias correction arena_adam_tick keeps on the device.
+// ---------------------------------------------------------------------------------------------
+struct OptHyper {
+  float lr;             // replaced by *lr_ptr when that is set
+  const float* lr_ptr;  // device learning rate (DeviceLR), or null
+  const float* corr;    // Adam: the clock's sqrt(1 - b2^t) / (1 - b1^t); RMSProp: null
+  float a, oma;         // RMSProp: rho, 1 - rho;  Adam: b1, 1 - b1
+  float b, omb;         // RMSProp: mu, unused;    Adam: b2, 1 - b2
+  float eps, wd, scale;
+};
+
+// The per-launch step size: lr for RMSProp, lr * corr for Adam.
+template <bool ADAM>
+__device__ __forceinline__ float opt_step_size(const OptHyper& h) {
+  const float lr = h.lr_ptr ? *h.lr_ptr : h.lr;
+  if constexpr (ADAM) return lr * *h.corr;
+  return lr;
+}
+
+template <bool ADAM>
+__device__ __forceinline__ void opt_1(float g, float& w, float& s0, float& s1, float step,
+                                      const OptHyper& h) {
+  const float d = g * h.scale + h.wd * w;
+  if constexpr (ADAM) {
+    s0 = h.a * s0 + h.oma * d;
+    s1 = h.b * s1 + h.omb * (d * d);
+    w = w - step * s0 / (sqrtf(s1) + h.eps);
+  } else {
+    s0 = h.a * s0 + h.oma * (d * d);
+    s1 = h.b * s1 + step * d / sqrtf(s0 + h.eps);
+    w = w - s1;
+  }
+}
+
+// bf16 gradients, fp32 masters, rounded bf16 weight to wbf: mt_sgd_master_kernel's layout with a
+// second state buffer (28 bytes per element against 22). n % 4 == 0 and offsets % 4 == 0.
+template <bool ADAM>
+__global__ __launch_bounds__(256) void mt_opt_master_kernel(MtArgs a, float* __restrict__ master,
+                                                            float* __restrict__ st0,
+                                                            float* __restrict__ st1,
+                                                            uint16_t* __restrict__ wbf,
+                                                            OptHyper h) {
+  const float step = opt_step_size<ADAM>(h);
+  int ti = 0;
+  for (int i = 1; i < a.count; ++i)
+    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
+  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
+  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
+  const long long o = a.off[ti] + j;
+  const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j);
+  float4 w4 = *reinterpret_cast<const float4*>(master + o);
+  float4 p4 = *reinterpret_cast<const float4*>(st0 + o);
+  float4 q4 = *reinterpret_cast<const float4*>(st1 + o);
+  const float g[4] = {bf16_to_f32(g2.x & 0xffffu), bf16_to_f32(g2.x >> 16),
+                      bf16_to_f32(g2.y & 0xffffu), bf16_to_f32(g2.y >> 16)};
+  float* w = &w4.x;
+  float* p = &p4.x;
+  float* q = &q4.x;
+  uint32_t r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    opt_1<ADAM>(g[k], w[k], p[k], q[k], step, h);
+    r[k] = f32_to_bf16(w[k]);
+  }
+  *reinterpret_cast<float4*>(master + o) = w4;
+  *reinterpret_cast<float4*>(st0 + o) = p4;
+  *reinterpret_cast<float4*>(st1 + o) = q4;
+  *reinterpret_cast<uint2*>(wbf + o) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+}
+
+// fp32 parameters with fp32 gradients (the BN / bias group): mt_sgd_f32_kernel's walk, any n and
+// any offset, 16-byte accesses under the same alignment test, else one element at a time.
+template <bool ADAM>
+__global__ __launch_bounds__(256) void mt_opt_f32_kernel(MtArgs a, float* __restrict__ wflat,
+                                                         float* __restrict__ st0,
+                                                         float* __restrict__ st1, OptHyper h) {
+  const float step = opt_step_size<ADAM>(h);
+  int ti = 0;
+  for (int i = 1; i < a.count; ++i)
+    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
+  const long long n = a.n[ti];
+  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
+  if (j >= n) return;
+  const float* g = a.ptr[ti] + j;
+  float* w = wflat + a.off[ti] + j;
+  float* p = st0 + a.off[ti] + j;
+  float* q = st1 + a.off[ti] + j;
+  // the flat buffers are 16-byte aligned (host-checked), so the segment is when its offset is
+  const bool vec = j + 4 <= n && (a.off[ti] & 3) == 0 &&
+                   (reinterpret_cast<uintptr_t>(a.ptr[ti]) & 15) == 0;
+  if (vec) {
+    const float4 g4 = *reinterpret_cast<const float4*>(g);
+    float4 w4 = *reinterpret_cast<const float4*>(w);
+    float4 p4 = *reinterpret_cast<const float4*>(p);
+    float4 q4 = *reinterpret_cast<const float4*>(q);
+    opt_1<ADAM>(g4.x, w4.x, p4.x, q4.x, step, h);
+    opt_1<ADAM>(g4.y, w4.y, p4.y, q4.y, step, h);
+    opt_1<ADAM>(g4.z, w4.z, p4.z, q4.z, step, h);
+    opt_1<ADAM>(g4.w, w4.w, p4.w, q4.w, step, h);
+    *reinterpret_cast<float4*>(w) = w4;
+    *reinterpret_cast<float4*>(p) = p4;
+    *reinterpret_cast<float4*>(q) = q4;
+  } else {
+    for (int k = 0; k < 4 && j + k < n; ++k) {
+      float wk = w[k], pk = p[k], qk = q[k];
+      opt_1<ADAM>(g[k], wk, pk, qk, step, h);
+      w[k] = wk;
+      p[k] = pk;
+      q[k] = qk;
+    }
+  }
+}
+
+// Adam's clock (arena_amd/ops/optim.py AdamClock), advanced on the device so a captured step
+// keeps correcting the bias from replay to replay. One lane: pw[0] = b1^t and pw[1] = b2^t as
+// running fp64 products, corr = float(sqrt(1 - b2^t) / (1 - b1^t)) with every fp64 operation
+// rounded on its own, exactly as reference_adam_corr does in Python floats. As in
+// lr_schedule_kernel, the empty asm keeps -ffp-contract=fast from fusing each product into the
+// subtraction that follows it.
+__global__ void adam_tick_kernel(long long* __restrict__ step, double* __restrict__ pw,
+                                 float* __restrict__ corr, double b1, double b2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double p1 = pw[0] * b1;
+  double p2 = pw[1] * b2;
+  asm volatile("" : "+v"(p1));
+  asm volatile("" : "+v"(p2));
+  pw[0] = p1;
+  pw[1] = p2;
+  *corr = (float)(sqrt(1.0 - p2) / (1.0 - p1));
+  *step = *step + 1;
+}
+
+// Fills MtArgs for tensors [base, base + cnt) and returns the launch's block count.
+inline int mt_fill(MtArgs& a, const void* const* ptrs, const long long* offs, const long long* ns,
+                   int base, int cnt) {
+  int blocks = 0;
+  for (int i = 0; i < cnt; ++i) {
+    a.ptr[i] = const_cast<float*>(reinterpret_cast<const float*>(ptrs[base + i]));
+    a.off[i] = offs[base + i];
+    a.n[i] = ns[base + i];
+    a.blk_begin[i] = blocks;
+    blocks += (int)((ns[base + i] + 1023) / 1024);
+  }
+  a.blk_begin[cnt] = blocks;
+  a.count = cnt;
+  return blocks;
+}
+
+template <bool ADAM>
+hipError_t launch_opt_master(const void* const* grads, const long long* offs, const long long* ns,
+                             int count, float* master, float* st0, float* st1, void* wbf,
+                             const OptHyper& h, hipStream_t stream) {
+  if (ADAM && !h.corr) return hipErrorInvalidValue;
+  for (int i = 0; i < count; ++i)
+    if (ns[i] < 0 || offs[i] < 0 || ns[i] % 4 || offs[i] % 4) return hipErrorInvalidValue;
+  for (int base = 0; base < count; base += kMtMax) {
+    MtArgs a;
+    const int blocks = mt_fill(a, grads, offs, ns, base, std::min(kMtMax, count - base));
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(mt_opt_master_kernel<ADAM>, dim3(blocks), dim3(256), 0, stream, a, master,
+                       st0, st1, reinterpret_cast<uint16_t*>(wbf), h);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <bool ADAM>
+hipError_t launch_opt_f32(const float* const* grads, const long long* offs, const long long* ns,
+                          int count, float* w, float* st0, float* st1, const OptHyper& h,
+                          hipStream_t stream) {
+  if (ADAM && !h.corr) return hipErrorInvalidValue;
+  for (int i = 0; i < count; ++i)
+    if (ns[i] < 0 || offs[i] < 0) return hipErrorInvalidValue;
+  for (int base = 0; base < count; base += kMtMax) {
+    MtArgs a;
+    const int blocks = mt_fill(a, reinterpret_cast<const void* const*>(grads), offs, ns, base,
+                               std::min(kMtMax, count - base));
+    if (blocks == 0) continue;
+    hipLaunchKernelGGL(mt_opt_f32_kernel<ADAM>, dim3(blocks), dim3(256), 0, stream, a, w, st0, st1,
+                       h);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1665,6 +1861,48 @@ hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, f
                              hipStream_t stream) {
   if (n_seg < 1 || n_seg > 64) return hipErrorInvalidValue;
   hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, seg, n_seg, step, lr);
+  return hipGetLastError();
+}
+
+// RMSProp / Adam over bf16 gradients with fp32 masters: offs / ns multiples of 4, as
+// arena_mt_sgd_master. omr, omb1, omb2: 1 - rho, 1 - b1, 1 - b2, formed by the caller in fp64.
+hipError_t arena_mt_rmsprop_master(const void* const* grads, const long long* offs,
+                                   const long long* ns, int count, float* master, float* ms,
+                                   float* mom, void* wbf, float lr, const float* lr_ptr, float rho,
+                                   float omr, float mu, float eps, float wd, hipStream_t stream) {
+  const OptHyper h{lr, lr_ptr, nullptr, rho, omr, mu, 0.f, eps, wd, 1.f};
+  return launch_opt_master<false>(grads, offs, ns, count, master, ms, mom, wbf, h, stream);
+}
+
+hipError_t arena_mt_adam_master(const void* const* grads, const long long* offs,
+                                const long long* ns, int count, float* master, float* m, float* v,
+                                void* wbf, float lr, const float* lr_ptr, const float* corr,
+                                float b1, float omb1, float b2, float omb2, float eps, float wd,
+                                hipStream_t stream) {
+  const OptHyper h{lr, lr_ptr, corr, b1, omb1, b2, omb2, eps, wd, 1.f};
+  return launch_opt_master<true>(grads, offs, ns, count, master, m, v, wbf, h, stream);
+}
+
+// The same over fp32 tensors with fp32 gradients (any sizes and offsets), as arena_mt_sgd_f32.
+hipError_t arena_mt_rmsprop_f32(const float* const* grads, const long long* offs,
+                                const long long* ns, int count, float* w, float* ms, float* mom,
+                                float lr, const float* lr_ptr, float rho, float omr, float mu,
+                                float eps, float wd, float scale, hipStream_t stream) {
+  const OptHyper h{lr, lr_ptr, nullptr, rho, omr, mu, 0.f, eps, wd, scale};
+  return launch_opt_f32<false>(grads, offs, ns, count, w, ms, mom, h, stream);
+}
+
+hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, const long long* ns,
+                             int count, float* w, float* m, float* v, float lr,
+                             const float* lr_ptr, const float* corr, float b1, float omb1, float b2,
+                             float omb2, float eps, float wd, float scale, hipStream_t stream) {
+  const OptHyper h{lr, lr_ptr, corr, b1, omb1, b2, omb2, eps, wd, scale};
+  return launch_opt_f32<true>(grads, offs, ns, count, w, m, v, h, stream);
+}
+
+hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, step, pw, corr, b1, b2);
   return hipGetLastError();
 }
 
