@@ -8,7 +8,8 @@ This is the same workload, built for MI355X:
 * ResNet v1.5 (``arena_amd.models.resnet``), NHWC (``channels_last``), bf16 autocast on the MFMA
   conv/GEMM paths, fp32 master weights;
 * momentum SGD with weight decay, as in tf_cnn_benchmarks; ``--optimizer`` selects its plain
-  SGD, RMSProp or Adam instead (TF1's forms; fused master-weight kernels on one rank);
+  SGD, RMSProp or Adam instead (TF1's forms; fused master-weight kernels on one rank), and
+  ``--lars`` scales momentum SGD's rate per weight tensor (norms reduced on the device);
 * one process per GPU: ``hvd.DistributedOptimizer`` buckets (RCCL or the xGMI kernel on a comm
   stream) overlap the gradient allreduce with backward;
 * output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``;
@@ -99,6 +100,17 @@ def parse(argv=None):
     ap.add_argument("--adam_beta1", type=float, default=None, help="default 0.9")
     ap.add_argument("--adam_beta2", type=float, default=None, help="default 0.999")
     ap.add_argument("--adam_epsilon", type=float, default=None, help="default 1e-8")
+    ap.add_argument("--lars", action="store_true",
+                    help="layer-wise adaptive rate scaling on top of --optimizer momentum / sgd "
+                         "(tf.contrib's LARSOptimizer, the MLPerf ResNet form): every conv / fc "
+                         "weight steps with lr * eeta * |w| / (|g| + weight_decay * |w| + "
+                         "epsilon); BatchNorm scales / shifts and biases keep plain momentum SGD. "
+                         "With master weights on one rank the norms and the update are fused "
+                         "kernels inside the captured step, else plain tensor ops")
+    ap.add_argument("--lars_eeta", type=float, default=None,
+                    help="LARS trust coefficient (default 0.001)")
+    ap.add_argument("--lars_epsilon", type=float, default=None,
+                    help="added to the trust ratio's denominator (default 0.0)")
     ap.add_argument("--weight_decay", type=float, default=4e-5)
     ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
     ap.add_argument("--data_format", choices=["NHWC", "NCHW"], default="NHWC")
@@ -209,6 +221,18 @@ def parse(argv=None):
             elif not 0.0 <= v < 1.0:
                 ap.error(f"--{f} must lie in [0, 1)")
             setattr(args, f, v)
+    given = [f for f in LARS_FLAGS if getattr(args, f) is not None]
+    if given and not args.lars:
+        ap.error(f"--{given[0]} needs --lars")
+    if args.lars and args.optimizer not in ("momentum", "sgd"):
+        ap.error(f"--lars modifies --optimizer momentum / sgd, not {args.optimizer}")
+    for f, default in LARS_FLAGS.items():
+        if getattr(args, f) is None:
+            setattr(args, f, default)
+    if not args.lars_eeta > 0.0:
+        ap.error("--lars_eeta must be > 0")
+    if not args.lars_epsilon >= 0.0:
+        ap.error("--lars_epsilon must be >= 0")
     return args
 
 
@@ -217,6 +241,9 @@ OPTIMIZER_FLAGS = {
     "rmsprop": {"rmsprop_decay": 0.9, "rmsprop_momentum": 0.9, "rmsprop_epsilon": 1.0},
     "adam": {"adam_beta1": 0.9, "adam_beta2": 0.999, "adam_epsilon": 1e-8},
 }
+
+# the flags that belong to --lars, with the MLPerf ResNet reference's defaults
+LARS_FLAGS = {"lars_eeta": 0.001, "lars_epsilon": 0.0}
 
 
 IMAGENET_TRAIN_IMAGES = 1281167    # tf_cnn_benchmarks' epoch when no dataset defines one
@@ -343,6 +370,14 @@ def build(args, dev, world, segments=None):
                              "update of data-parallel master weights (ShardedMasterSGD) implements "
                              "momentum SGD only; use --master_weights off")
         mw = "off"
+    lars = bool(getattr(args, "lars", False))
+    if lars and world > 1:
+        if mw == "on":
+            raise SystemExit("--lars --master_weights on: the sharded xGMI / RCCL update of "
+                             "data-parallel master weights (ShardedMasterSGD) implements momentum "
+                             "SGD only (LARS needs per-tensor norms across shards); use "
+                             "--master_weights off")
+        mw = "off"
     model = build_model(args, dev)
     decay, no_decay = [], []
     for n, p in model.named_parameters():
@@ -377,6 +412,8 @@ def build(args, dev, world, segments=None):
         pass                   # data parallel, sharded
     elif name in ("rmsprop", "adam"):
         opt = build_rmsprop_or_adam(args, name, decay, no_decay, lr if master else None)
+    elif lars:
+        opt = build_lars(args, momentum, decay, no_decay, lr if master else None)
     elif master and sched is not None:
         # as below, with the BN / bias group on the multi-tensor kernel that reads the device lr
         from ..ops.optim import MasterSGD, MultiTensorSGD32, OptimizerGroup
@@ -426,6 +463,24 @@ def build_rmsprop_or_adam(args, name, decay, no_decay, master_lr):
     if name == "adam":
         hyper["clock"] = first.clock
     return optim.OptimizerGroup(first, fused_pair[1](no_decay, lr=master_lr, **hyper))
+
+
+def build_lars(args, momentum, decay, no_decay, master_lr):
+    """``--lars``. ``master_lr`` (a float or a ``DeviceLR``): ``MasterLARS`` over the decayed
+    weights (bf16 with fp32 masters; norms, trust ratio and update on the device) and the BN /
+    bias group, LARS's skip list, on ``MultiTensorSGD32``. None: ``TFLars``, the same formula in
+    plain tensor ops over fp32 parameters."""
+    from ..ops import optim
+    hyper = {"eeta": getattr(args, "lars_eeta", LARS_FLAGS["lars_eeta"]),
+             "eps": getattr(args, "lars_epsilon", LARS_FLAGS["lars_epsilon"])}
+    if master_lr is None:
+        return optim.TFLars([{"params": decay, "weight_decay": args.weight_decay, "lars": True},
+                             {"params": no_decay, "weight_decay": 0.0, "lars": False}],
+                            lr=args.learning_rate, momentum=momentum, **hyper)
+    return optim.OptimizerGroup(
+        optim.MasterLARS(decay, lr=master_lr, momentum=momentum, weight_decay=args.weight_decay,
+                         **hyper),
+        optim.MultiTensorSGD32(no_decay, lr=master_lr, momentum=momentum))
 
 
 def schedule_of(opt):
@@ -690,6 +745,7 @@ def main(argv=None) -> int:
                    "ms_per_step": round(elapsed / args.num_batches * 1e3, 3),
                    "batch_per_device": args.batch_size, "devices": world,
                    "dtype": args.dtype, "comm": comm_name(opt), "optimizer": args.optimizer,
+                   "lars": bool(args.lars),
                    "exec": "hipgraph" if graph is not None else "eager",
                    "final_loss": round(float(loss), 4)}
             if counts is not None:

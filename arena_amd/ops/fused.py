@@ -249,6 +249,30 @@ def mt_adam_f32(grads: Sequence[Tensor], offsets: Sequence[int], w: Tensor, m: T
                          float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w))
 
 
+def mt_lars_workspace_floats(numels: Sequence[int]) -> int:
+    """fp32 elements of :func:`mt_lars_master`'s ``workspace`` for tensors of these sizes: one
+    (sum w^2, sum g^2) pair per 1024-element block."""
+    return 2 * sum((int(n) + 1023) // 1024 for n in numels)
+
+
+def mt_lars_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tensor, mom: Tensor,
+                   wbf: Tensor, trust: Tensor, slots: Sequence[int], workspace: Tensor, *,
+                   lr: float, momentum: float, weight_decay: float = 0.0, eeta: float = 0.001,
+                   eps: float = 0.0, lr_t: Optional[Tensor] = None) -> None:
+    """LARS over bf16 grads with fp32 masters (the layout of :func:`mt_sgd_master`), two launches
+    per 48 tensors: per-block partial sums of w^2 and g^2 into ``workspace``, then the update,
+    which reduces them per tensor on the device: trust = eeta * |w| / (|g| + wd * |w| + eps) (1.0
+    when a norm is 0); m = momentum * m + (g + wd * w); w -= (lr * trust) * m; ``wbf`` gets the
+    rounded bf16 weights. ``trust`` (fp32) receives tensor i's ratio at ``slots[i]``; the other
+    entries keep their values. ``workspace``: fp32, at least
+    :func:`mt_lars_workspace_floats` elements, contents irrelevant. Deterministic: no atomics.
+    Semantics: :mod:`arena_amd.ops.reference`."""
+    _impl(master).mt_lars_master(list(grads), [int(o) for o in offsets], master, mom, wbf, trust,
+                                 [int(s) for s in slots], workspace, float(lr), float(momentum),
+                                 float(weight_decay), float(eeta), float(eps),
+                                 lr_t=_check_lr_t(lr_t, master))
+
+
 def adam_tick(step: Tensor, pow: Tensor, corr: Tensor, b1: float, b2: float) -> None:
     """One tick of Adam's device clock, in one launch: ``pow *= (b1, b2)`` (fp64 running products
     ``b1^t``, ``b2^t``), ``corr[0] = float32(sqrt(1 - pow[1]) / (1 - pow[0]))``, ``step[0] += 1``

@@ -19,9 +19,13 @@ tf_cnn_benchmarks' ``--optimizer`` defaults assume; :mod:`arena_amd.ops.referenc
 Adam's bias correction depends on the step count, which a captured graph would bake in, so it
 lives on the device in an :class:`AdamClock` that one one-lane kernel advances per step.
 
-:class:`TFRMSprop` and :class:`TFAdam` are the same formulas as ``torch.optim.Optimizer``
-subclasses in plain tensor ops, for the paths without a fused kernel (CPU, fp32 weights, data
-parallel under ``hvd.DistributedOptimizer``).
+:class:`MasterLARS` is :class:`MasterSGD` with LARS's per-tensor trust ratio: the two L2 norms it
+needs are reduced on the device (per-block partials, then a fixed-order sum inside the update
+kernel), so the captured step has no host read. Its BN / bias group is :class:`MultiTensorSGD32`.
+
+:class:`TFRMSprop`, :class:`TFAdam` and :class:`TFLars` are the same formulas as
+``torch.optim.Optimizer`` subclasses in plain tensor ops, for the paths without a fused kernel
+(CPU, fp32 weights, data parallel under ``hvd.DistributedOptimizer``).
 """
 from __future__ import annotations
 
@@ -400,6 +404,46 @@ class MultiTensorSGD32(_Flat32Optimizer):
                          weight_decay=self.weight_decay, scale=self.scale, **_lr_args(self.lr))
 
 
+# ---------------------------------------------------------------------------------------- LARS
+def _non_negative(name: str, v: float) -> float:
+    v = float(v)
+    if not v >= 0.0:
+        raise ValueError(f"{name} must be >= 0, got {v}")
+    return v
+
+
+class MasterLARS(_MasterOptimizer):
+    """LARS (tf.contrib's ``LARSOptimizer``, the MLPerf ResNet form;
+    :mod:`arena_amd.ops.reference` defines it) with fp32 master weights: :class:`MasterSGD`'s
+    design with the step ``lr * trust``, ``trust = eeta * |w| / (|g| + weight_decay * |w| + eps)``
+    per tensor (1.0 when a norm is 0). The norms, the ratio and the update run on the device in
+    two ``mt_lars_master`` launches per 48 tensors, without atomics, so a captured step replays
+    it. ``trust`` (fp32, one entry per parameter, 1.0 until the parameter's first update) holds
+    the ratios of the last step; it is derived, not state. The BN / bias group next to it is
+    :class:`MultiTensorSGD32` (LARS's skip list: plain momentum SGD, no weight decay)."""
+
+    _STATE = (("mom", "momentum_buffer", 0.0),)
+    _HYPER = ("momentum", "weight_decay", "eeta", "eps")
+
+    def __init__(self, params: Iterable[Tensor], lr: Union[float, DeviceLR], momentum: float = 0.9,
+                 weight_decay: float = 0.0, eeta: float = 0.001, eps: float = 0.0):
+        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self.eeta, self.eps = _positive("eeta", eeta), _non_negative("eps", eps)
+        self._init_master(params, lr)
+        dev = self.master.device
+        self.trust = torch.ones(len(self.params), dtype=torch.float32, device=dev)
+        self.workspace = torch.empty(
+            fused.mt_lars_workspace_floats([p.numel() for p in self.params]),
+            dtype=torch.float32, device=dev)
+        self._slot = {off: i for i, off in enumerate(self.offsets)}
+
+    def _update(self, grads, offs) -> None:
+        fused.mt_lars_master(grads, offs, self.master, self.mom, self.wbf, self.trust,
+                             [self._slot[o] for o in offs], self.workspace,
+                             momentum=self.momentum, weight_decay=self.weight_decay,
+                             eeta=self.eeta, eps=self.eps, **_lr_args(self.lr))
+
+
 # ------------------------------------------------------------------------------------- RMSProp
 class _RMSpropHyper:
     """TF1's non-centred RMSProp: ``ms`` starts at 1.0 as TF's slot does, ``mom`` at 0."""
@@ -687,3 +731,52 @@ class TFAdam(torch.optim.Optimizer):
         self._betas_t.copy_(torch.tensor(self.betas, dtype=torch.float64))
         self.step_count.fill_(int(clock["step"]))
         self.pow.copy_(torch.tensor(clock["pow"], dtype=torch.float64))
+
+
+class TFLars(torch.optim.Optimizer):
+    """LARS (:mod:`arena_amd.ops.reference`'s form) in plain tensor ops on any device, for the
+    paths without the fused kernel: momentum SGD whose step is ``lr * trust`` with ``trust = eeta
+    * |w| / (|g| + weight_decay * |w| + eps)`` per tensor, 1.0 when a norm is 0. Param groups
+    carry ``lars: bool``; a group with ``lars=False`` (BN scales / shifts, biases: LARS's skip
+    list) takes plain momentum SGD with its own ``weight_decay``. The norms and the guard stay on
+    the device (no host read), so a captured step replays correctly; ``lr`` is read from
+    ``param_groups`` at every (eager) step."""
+
+    def __init__(self, params, lr: float, momentum: float = 0.9, eeta: float = 0.001,
+                 eps: float = 0.0, weight_decay: float = 0.0):
+        super().__init__(params, dict(lr=float(lr), momentum=_unit_interval("momentum", momentum),
+                                      eeta=_positive("eeta", eeta), eps=_non_negative("eps", eps),
+                                      weight_decay=float(weight_decay), lars=True))
+        for group in self.param_groups:    # now, not at the first step: that one may be captured
+            for p in group["params"]:
+                self._init_state(p)
+
+    def _init_state(self, p: Tensor) -> dict:
+        st = self.state[p]
+        st["mom"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            lr, mu, wd = group["lr"], group["momentum"], group["weight_decay"]
+            eeta, eps = group["eeta"], group["eps"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                mom = (self.state[p] or self._init_state(p))["mom"]
+                g = p.grad.to(p.dtype)
+                step = lr
+                if group["lars"]:
+                    wn = torch.linalg.vector_norm(p)
+                    gn = torch.linalg.vector_norm(g)
+                    trust = torch.where((wn > 0) & (gn > 0), eeta * wn / (gn + wd * wn + eps),
+                                        torch.ones_like(wn))
+                    step = lr * trust
+                mom.mul_(mu).add_(g + wd * p)
+                p.sub_(step * mom)
+        return loss

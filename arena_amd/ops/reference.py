@@ -408,6 +408,59 @@ def mt_adam_f32(grads, offsets, w, m, v, corr, lr, b1, omb1, b2, omb2, eps, weig
               scale)
 
 
+# ------------------------------------------------------------------------------------------------
+# LARS (layer-wise adaptive rate scaling), tf.contrib's LARSOptimizer as the MLPerf ResNet
+# reference uses it: momentum SGD whose learning rate is scaled per tensor. Defined once, here; the
+# HIP kernels (``mt_lars_*_kernel`` in csrc/ops/mlp_kernels.hip), ``MasterLARS`` / ``TFLars`` and
+# the tests follow it. For a tensor with fp32 master w, bf16 gradient g and momentum m:
+#
+#       wn = ||w||2            gn = ||g||2
+#       trust = eeta * wn / (gn + wd * wn + eps)    if wn > 0 and gn > 0, else 1.0
+#       step  = lr * trust
+#       m = mu * m + (g + wd * w)
+#       w = w - step * m                            wbf = bf16(w)
+#
+# The norms are fp64 sums over the squares of the fp32 values in memory order (the bf16 gradient
+# widens to fp32 exactly), ``wn`` and ``gn`` are ``float32(sqrt(sum))``, ``trust`` and ``step``
+# are fp32 operations in the order written, and the last two lines are ``mt_sgd_master``'s. A
+# kernel may sum in any fixed order, in fp32 or wider. BatchNorm scales / shifts and biases are on
+# LARS's skip list: they keep plain momentum SGD without weight decay (``mt_sgd_f32``).
+# ------------------------------------------------------------------------------------------------
+def _sum_squares(v: torch.Tensor) -> float:
+    """The fp64 sum of the squares of ``v``'s fp32 values, in memory order."""
+    if v.numel() == 0:
+        return 0.0
+    d = v.double()
+    return float(torch.cumsum(d * d, 0)[-1])
+
+
+def reference_lars_trust(w, g, eeta, weight_decay, eps) -> torch.Tensor:
+    """LARS's trust ratio of one tensor (flat fp32 ``w`` and ``g``) as an fp32 scalar tensor."""
+    wn = _f32(math.sqrt(_sum_squares(w)))
+    gn = _f32(math.sqrt(_sum_squares(g)))
+    if not (wn > 0 and gn > 0):
+        return _f32(1.0)
+    return _f32(eeta) * wn / (gn + _f32(weight_decay) * wn + _f32(eps))
+
+
+def mt_lars_master(grads, offsets, master, mom, wbf, trust, slots, workspace, lr, momentum,
+                   weight_decay, eeta, eps, lr_t=None):
+    """CPU reference of the HIP ``mt_lars_master`` kernels (``workspace`` is not used)."""
+    lr = _f32(_lr_value(lr, lr_t))
+    for g, off, slot in zip(grads, offsets, slots):
+        n = g.numel()
+        if n == 0:
+            continue
+        w, m = master[off:off + n], mom[off:off + n]
+        g32 = _storage_flat(g).float()
+        t = reference_lars_trust(w, g32, eeta, weight_decay, eps)
+        trust[slot] = t
+        step = lr * t
+        m.mul_(momentum).add_(g32 + weight_decay * w)
+        w.sub_(step * m)
+        wbf[off:off + n].copy_(w)
+
+
 def lr_schedule(table, step, lr):
     """CPU form of the ``arena_lr_schedule`` kernel: decodes the device table and evaluates
     :func:`arena_amd.ops.schedule.reference_lr`."""

@@ -276,6 +276,17 @@ hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, c
                              int count, float* w, float* m, float* v, float lr,
                              const float* lr_ptr, const float* corr, float b1, float omb1, float b2,
                              float omb2, float eps, float wd, float scale, hipStream_t stream);
+// LARS (arena_amd/ops/reference.py) over bf16 gradients with fp32 masters, two launches per 48
+// tensors: per-block partial sums of w^2 and g^2 into workspace, then the update, whose blocks
+// each reduce their tensor's partials, form trust = eeta * |w| / (|g| + wd * |w| + eps) (1 when a
+// norm is 0) and step with lr * trust. trust[slots[i]] receives tensor i's ratio. workspace:
+// arena_mt_lars_workspace_floats(ns, count) floats, 16-byte aligned, never read before written.
+long long arena_mt_lars_workspace_floats(const long long* ns, int count);
+hipError_t arena_mt_lars_master(const void* const* grads, const long long* offs,
+                                const long long* ns, const int* slots, int count, float* master,
+                                float* mom, void* wbf, float* trust, float* workspace, float lr,
+                                const float* lr_ptr, float mu, float wd, float eeta, float eps,
+                                hipStream_t stream);
 // t = *step + 1; pw[0] *= b1; pw[1] *= b2; *corr = float(sqrt(1 - pw[1]) / (1 - pw[0])) in fp64,
 // every operation rounded on its own; *step = t.
 hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,

@@ -700,6 +700,40 @@ void mt_adam_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Ten
             "mt_adam_master");
 }
 
+// LARS: master_segments' checks (mom is the one state buffer) plus trust / slots / workspace /
+// eeta / eps, all before the first launch.
+void mt_lars_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
+                    Tensor mom, Tensor wbf, Tensor trust, std::vector<int64_t> slots,
+                    Tensor workspace, double lr, double momentum, double weight_decay, double eeta,
+                    double eps, OptT lr_t) {
+  const MtSegments s = master_segments(grads, offsets, master, mom, mom, wbf, "mt_lars_master");
+  const float* lp = opt_lr_ptr(lr_t, master, "mt_lars_master");
+  check_f32(trust, "trust");
+  check_f32(workspace, "workspace");
+  TORCH_CHECK(trust.device() == master.device() && workspace.device() == master.device(),
+              "mt_lars_master: trust and workspace must be on the master buffer's GPU");
+  TORCH_CHECK(slots.size() == grads.size(), "mt_lars_master: slots length");
+  std::vector<int> sl;
+  for (size_t i = 0; i < slots.size(); ++i) {
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < trust.numel(), "mt_lars_master: slot ", i, " (",
+                slots[i], ") out of range of trust's ", trust.numel(), " entries");
+    sl.push_back((int)slots[i]);
+  }
+  const long long need = arena_mt_lars_workspace_floats(s.ns.data(), (int)s.ns.size());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(workspace.data_ptr()) % 16 == 0,
+              "mt_lars_master: workspace must be 16-byte aligned");
+  TORCH_CHECK(workspace.numel() >= need, "mt_lars_master: workspace holds ", workspace.numel(),
+              " floats, these tensors' blocks need ", need);
+  TORCH_CHECK((float)eeta > 0.f, "mt_lars_master: eeta must be > 0");
+  TORCH_CHECK((float)eps >= 0.f, "mt_lars_master: eps must be >= 0");
+  check_hip(arena_mt_lars_master(s.ptrs.data(), s.offs.data(), s.ns.data(), sl.data(),
+                                 (int)s.ptrs.size(), master.data_ptr<float>(),
+                                 mom.data_ptr<float>(), wbf.data_ptr(), trust.data_ptr<float>(),
+                                 workspace.data_ptr<float>(), (float)lr, lp, (float)momentum,
+                                 (float)weight_decay, (float)eeta, (float)eps, cur_stream()),
+            "mt_lars_master");
+}
+
 void mt_rmsprop_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor ms,
                     Tensor mom, double lr, double rho, double omr, double momentum, double eps,
                     double weight_decay, double scale, OptT lr_t) {
@@ -2336,6 +2370,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("master"), py::arg("m"), py::arg("v"), py::arg("wbf"), py::arg("corr"),
         py::arg("lr"), py::arg("b1"), py::arg("omb1"), py::arg("b2"), py::arg("omb2"),
         py::arg("eps"), py::arg("weight_decay"), py::arg("lr_t") = py::none());
+  m.def("mt_lars_master", &mt_lars_master, py::arg("grads"), py::arg("offsets"),
+        py::arg("master"), py::arg("mom"), py::arg("wbf"), py::arg("trust"), py::arg("slots"),
+        py::arg("workspace"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
+        py::arg("eeta"), py::arg("eps"), py::arg("lr_t") = py::none());
   m.def("mt_rmsprop_f32", &mt_rmsprop_f32, py::arg("grads"), py::arg("offsets"), py::arg("w"),
         py::arg("ms"), py::arg("mom"), py::arg("lr"), py::arg("rho"), py::arg("omr"),
         py::arg("momentum"), py::arg("eps"), py::arg("weight_decay"), py::arg("scale"),

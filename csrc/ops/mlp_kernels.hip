@@ -1531,6 +1531,137 @@ __global__ void adam_tick_kernel(long long* __restrict__ step, double* __restric
   *step = *step + 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// LARS (arena_amd/ops/reference.py defines it): momentum SGD over bf16 gradients with fp32
+// masters whose step is lr * trust, trust = eeta * |w| / (|g| + wd * |w| + eps) per tensor. Two
+// launches per group of 48 tensors over mt_sgd_master_kernel's walk (1024 elements per block):
+//   mt_lars_norms_kernel   one wave per chunk writes part[chunk] = (sum w^2, sum g^2): 16 serial
+//                          fp32 terms per lane, then the wave64 xor tree.
+//   mt_lars_update_kernel  every block sums ITS tensor's partials in fp64 (lane t takes partials
+//                          t, t + 256, ... in order, then the same tree), forms trust and applies
+//                          mt_sgd_master_kernel's update with step in place of lr.
+// No atomics and nothing to zero: every partial is overwritten at every step. All blocks of a
+// tensor run the same sums over the same values in the same order, so they hold the same trust
+// bit for bit; the tensor's first block stores it to trust[slot].
+// ---------------------------------------------------------------------------------------------
+struct LarsSlots {
+  int slot[kMtMax];  // trust[slot[i]] receives tensor i's trust ratio
+  int part_base;     // this launch group's first (w^2, g^2) pair in the workspace
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void mt_lars_norms_kernel(MtArgs a, LarsSlots s,
+                                                            const float* __restrict__ master,
+                                                            float2* __restrict__ part) {
+  // one wave per 1024-element chunk (the update kernel's block): no LDS, no barrier
+  const int chunk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (chunk >= a.blk_begin[a.count]) return;
+  int ti = 0;
+  for (int i = 1; i < a.count; ++i)
+    if (chunk >= a.blk_begin[i]) ti = i;
+  const long long n = a.n[ti];
+  const long long j0 = (long long)(chunk - a.blk_begin[ti]) * 1024 + (threadIdx.x & 63) * 4;
+  const uint16_t* gp = reinterpret_cast<const uint16_t*>(a.ptr[ti]);
+  const float* wp = master + a.off[ti];
+  uint2 g2[4];
+  float4 w4[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // n % 4 == 0 (host-checked): 4 whole elements or none
+    const long long j = j0 + k * 256;
+    const bool live = j < n;
+    g2[k] = live ? *reinterpret_cast<const uint2*>(gp + j) : make_uint2(0u, 0u);
+    w4[k] = live ? *reinterpret_cast<const float4*>(wp + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float sw = 0.f, sg = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float g[4] = {bf16_to_f32(g2[k].x & 0xffffu), bf16_to_f32(g2[k].x >> 16),
+                        bf16_to_f32(g2[k].y & 0xffffu), bf16_to_f32(g2[k].y >> 16)};
+    const float* w = &w4[k].x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      sw += w[e] * w[e];
+      sg += g[e] * g[e];
+    }
+  }
+  sw = wave_sum(sw);
+  sg = wave_sum(sg);
+  if ((threadIdx.x & 63) == 0) part[s.part_base + chunk] = make_float2(sw, sg);
+}
+
+__global__ __launch_bounds__(256) void mt_lars_update_kernel(
+    MtArgs a, LarsSlots s, float* __restrict__ master, float* __restrict__ mom,
+    uint16_t* __restrict__ wbf, const float2* __restrict__ part, float* __restrict__ trust_out,
+    float lr, const float* lr_ptr, float mu, float wd, float eeta, float eps) {
+  __shared__ double red[8];
+  if (lr_ptr) lr = *lr_ptr;  // device learning rate (schedules under graph replay)
+  int ti = 0;
+  for (int i = 1; i < a.count; ++i)
+    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
+  const int first = a.blk_begin[ti];
+  const int nb = a.blk_begin[ti + 1] - first;
+  const float2* p = part + s.part_base + first;
+  double sw = 0.0, sg = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 1024) {  // 4 loads in flight, summed in index order
+    float2 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      v[k] = i + k * 256 < nb ? p[i + k * 256] : make_float2(0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      sw += (double)v[k].x;
+      sg += (double)v[k].y;
+    }
+  }
+  sw = wave_sum_f64(sw);
+  sg = wave_sum_f64(sg);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sw;
+    red[4 + (threadIdx.x >> 6)] = sg;
+  }
+  __syncthreads();
+  const float wn = (float)sqrt(((red[0] + red[1]) + red[2]) + red[3]);
+  const float gn = (float)sqrt(((red[4] + red[5]) + red[6]) + red[7]);
+  float trust = 1.f;
+  if (wn > 0.f && gn > 0.f) {
+    // fp32 operations in the reference's order; as in lr_schedule_kernel, the empty asm keeps
+    // -ffp-contract=fast from fusing a product into the sum that follows it
+    float num = eeta * wn;
+    float dec = wd * wn;
+    asm volatile("" : "+v"(num));
+    asm volatile("" : "+v"(dec));
+    trust = num / ((gn + dec) + eps);
+  }
+  float step = lr * trust;
+  asm volatile("" : "+v"(step));
+  if ((int)blockIdx.x == first && threadIdx.x == 0) trust_out[s.slot[ti]] = trust;
+  const long long j = (long long)(blockIdx.x - first) * 1024 + threadIdx.x * 4;
+  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
+  const long long o = a.off[ti] + j;
+  const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j);
+  float4 w4 = *reinterpret_cast<const float4*>(master + o);
+  float4 m4 = *reinterpret_cast<const float4*>(mom + o);
+  const float g[4] = {bf16_to_f32(g2.x & 0xffffu), bf16_to_f32(g2.x >> 16),
+                      bf16_to_f32(g2.y & 0xffffu), bf16_to_f32(g2.y >> 16)};
+  float* w = &w4.x;
+  float* m = &m4.x;
+  uint32_t r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    m[k] = mu * m[k] + (g[k] + wd * w[k]);
+    w[k] = w[k] - step * m[k];
+    r[k] = f32_to_bf16(w[k]);
+  }
+  *reinterpret_cast<float4*>(master + o) = w4;
+  *reinterpret_cast<float4*>(mom + o) = m4;
+  *reinterpret_cast<uint2*>(wbf + o) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
+}
+
 // Fills MtArgs for tensors [base, base + cnt) and returns the launch's block count.
 inline int mt_fill(MtArgs& a, const void* const* ptrs, const long long* offs, const long long* ns,
                    int base, int cnt) {
@@ -1898,6 +2029,49 @@ hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, c
                              float omb2, float eps, float wd, float scale, hipStream_t stream) {
   const OptHyper h{lr, lr_ptr, corr, b1, omb1, b2, omb2, eps, wd, scale};
   return launch_opt_f32<true>(grads, offs, ns, count, w, m, v, h, stream);
+}
+
+long long arena_mt_lars_workspace_floats(const long long* ns, int count) {
+  long long blocks = 0;
+  for (int i = 0; i < count; ++i) blocks += (ns[i] + 1023) / 1024;
+  return 2 * blocks;
+}
+
+// LARS over bf16 gradients with fp32 masters: offs / ns multiples of 4, as arena_mt_sgd_master.
+// slots[i]: tensor i's entry of trust. workspace: arena_mt_lars_workspace_floats(ns, count) floats,
+// 16-byte aligned, contents irrelevant: one (w^2, g^2) pair per 1024-element block, each launch
+// group in its own range.
+hipError_t arena_mt_lars_master(const void* const* grads, const long long* offs,
+                                const long long* ns, const int* slots, int count, float* master,
+                                float* mom, void* wbf, float* trust, float* workspace, float lr,
+                                const float* lr_ptr, float mu, float wd, float eeta, float eps,
+                                hipStream_t stream) {
+  if (!trust || !workspace || !(eeta > 0.f) || !(eps >= 0.f)) return hipErrorInvalidValue;
+  for (int i = 0; i < count; ++i)
+    if (ns[i] < 0 || offs[i] < 0 || ns[i] % 4 || offs[i] % 4 || slots[i] < 0)
+      return hipErrorInvalidValue;
+  float2* part = reinterpret_cast<float2*>(workspace);
+  int part_base = 0;
+  for (int base = 0; base < count; base += kMtMax) {
+    MtArgs a;
+    LarsSlots s;
+    const int cnt = std::min(kMtMax, count - base);
+    const int blocks = mt_fill(a, grads, offs, ns, base, cnt);
+    if (blocks == 0) continue;
+    for (int i = 0; i < kMtMax; ++i) s.slot[i] = i < cnt ? slots[base + i] : 0;
+    s.part_base = part_base;
+    part_base += blocks;
+    hipLaunchKernelGGL(mt_lars_norms_kernel, dim3((blocks + 3) / 4), dim3(256), 0, stream, a, s,
+                       master, part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(mt_lars_update_kernel, dim3(blocks), dim3(256), 0, stream, a, s, master,
+                       mom, reinterpret_cast<uint16_t*>(wbf), part, trust, lr, lr_ptr, mu, wd,
+                       eeta, eps);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,
