@@ -10,6 +10,10 @@ Execution design:
     single launch -- no flatten/unflatten copies, no per-tensor launches.
   * The training set lives in HBM as uint8; the batch gather (permutation + device step counter)
     and the /255 dequantisation are fused into the first GEMM and the loss head.
+  * The batch of step t+1 does not depend on step t's parameters, so step t's backward launch
+    also copies it (u8 rows + labels) into the other half of a parity double buffer ``xa``/``ya``:
+    the forward loads its X rows from an address known at launch, next to its W loads, instead of
+    behind a step counter -> permutation -> row chain (``batch_ahead``, default on).
   * One step = 2 launches on one GPU: mlp_fwd_logits (hidden layer + per-tile partial logits,
     atomically accumulated) -> wgrad_grouped (every workgroup recomputes the 100x10 softmax-xent,
     derives dz in LDS, computes both layers' dW and applies Adam in its epilogue). No kernel
@@ -77,12 +81,17 @@ class FusedMLPTrainer:
     def __init__(self, cfg: MLPConfig, train_x: torch.Tensor, train_y: torch.Tensor,
                  device: torch.device | str = "cuda", process_group=None,
                  rank: int = 0, world: int = 1, external_update: bool = False,
-                 comm: str = "auto"):
+                 comm: str = "auto", batch_ahead: bool | None = None):
         """``external_update``: steps only produce the flat gradient ``G`` (the optimizer runs
         elsewhere -- the parameter server in PS mode); the step counter still advances.
         ``comm`` (data parallel on GPUs): "xgmi" = fused reduce-scatter/Adam/all-gather kernel over
         xGMI peer memory, "rccl" = graph-captured RCCL all_reduce + flat Adam, "auto" = xgmi when
-        its self-test passes on every rank of a single-node job, else rccl."""
+        its self-test passes on every rank of a single-node job, else rccl.
+        ``batch_ahead``: every backward launch publishes the next step's batch and the forward
+        reads it from there (see the module docstring); False = the forward gathers its rows
+        itself and publishes them for the backward. None = the ``ARENA_BATCH_AHEAD`` environment
+        switch (default 1). Inputs wider than the forward's training-step kernel handles
+        (``in_dim`` > 1024) always take the gathering path."""
         self.cfg = cfg
         self.external_update = external_update
         self.device = torch.device(device)
@@ -102,9 +111,9 @@ class FusedMLPTrainer:
         self._init_params()
         import os as _os
         self._x_from_dataset = _os.environ.get("ARENA_WGRAD_X", "published") == "dataset"
-        # forward row gather: "counter" (cursor -> permutation in the forward) or "rows" (the
-        # backward precomputes the next step's rows); measured equal-or-slower, so off by default
-        self._rows_ahead = _os.environ.get("ARENA_FWD_ROWS", "counter") == "rows"
+        if batch_ahead is None:
+            batch_ahead = _os.environ.get("ARENA_BATCH_AHEAD", "1") != "0"
+        self.batch_ahead = bool(batch_ahead) and D <= 1024
         self.xgmi = None
         if self.distributed:
             import torch.distributed as dist
@@ -134,6 +143,11 @@ class FusedMLPTrainer:
         self.logits2 = torch.zeros(2, B, C, device=dev)  # step-parity double buffer
         self.xb = torch.zeros(B, D, dtype=torch.uint8, device=dev)  # this step's gathered batch
         self.yb = torch.zeros(B, dtype=torch.int32, device=dev)
+        # batch ahead: before step t runs, xa[t & 1] / ya[t & 1] hold batch t. Backward t reads that
+        # half and fills the other with batch t + 1; _sync_rows re-establishes it from the host.
+        self.xa = torch.zeros(2, B, D, dtype=torch.uint8, device=dev)
+        self.ya = torch.zeros(2, B, dtype=torch.int32, device=dev)
+        self._ahead_step = -1   # the step xa / ya were prepared for (host-side tag)
         self.ctrA = torch.zeros(1, dtype=torch.int64, device=dev)
         self.ctrB = torch.zeros(1, dtype=torch.int64, device=dev)
         self.loss_hist = torch.zeros(cfg.hist_len, device=dev)
@@ -151,8 +165,7 @@ class FusedMLPTrainer:
         self.shard = self.shard.to(dev)
         self._gen = torch.Generator(device=dev).manual_seed(cfg.seed * 7919 + rank)
         self.perm = torch.empty(self.shard.numel(), dtype=torch.int32, device=dev)
-        # this step's dataset rows: written one step ahead by the backward kernel, so the forward
-        # reads them directly (host refreshes them when the permutation changes)
+        # the dataset rows of the batch the host last prepared (_sync_rows)
         self.rows = torch.empty(B, dtype=torch.int32, device=dev)
         self.steps_done = 0
         self._reshuffle()
@@ -215,10 +228,16 @@ class FusedMLPTrainer:
         self._sync_rows()
 
     def _sync_rows(self):
-        """rows = perm[(step * B + r) % len] for the next step (host-known step count)."""
+        """rows = perm[(step * B + r) % len] for the next step (host-known step count) and, with
+        ``batch_ahead``, that batch into its half of xa / ya. Stream-ordered, no host sync."""
         B, L = self.cfg.batch, self.perm.numel()
         pos = (self.steps_done * B + torch.arange(B, device=self.device)) % L
         self.rows.copy_(self.perm[pos])
+        if self.batch_ahead:
+            par, r = self.steps_done & 1, self.rows.to(torch.int64)
+            self.xa[par].copy_(self.train_x[r])
+            self.ya[par].copy_(self.train_y[r].to(torch.int32))
+            self._ahead_step = self.steps_done
 
     def pick_steps_per_graph(self, cap: int = 64, runs=()) -> int:
         """Largest divisor of the epoch length <= cap, so graphs never straddle a reshuffle.
@@ -245,38 +264,45 @@ class FusedMLPTrainer:
                 self._launch_step_part(part, parity)
             return
         if self.external_update:
-            self._launch_fwd_head()
+            self._launch_fwd_head(parity)
             self._launch_wgrad(adam=False, commit=True, parity=parity)
             return
-        self._launch_fwd_head()
+        self._launch_fwd_head(parity)
         self._launch_wgrad(adam=True, parity=parity)
 
-    def _launch_fwd_head(self):
+    def _launch_fwd_head(self, parity: int = -1):
         """Hidden layer + logits accumulation (one launch); writes B = A + 1."""
         cfg, B, A, Bc = self.cfg, self.cfg.batch, self.ctrA, self.ctrB
-        ops.mlp_fwd_logits(self.train_x, self.W1, self.b1, self.Hbuf, self.W2, self.logits2,
-                           W2_copy=self.W2snap, xb=self.xb, labels=self.train_y, yb=self.yb,
-                           x_scale=1.0 / 255.0, idx=self.perm, cursor=A,
-                           batch=B, keep_prob=cfg.keep_prob,
-                           seed=cfg.seed * 2654435761 + self.rank, step=A, ctr_dst=Bc,
-                           ctr_src=A, ctr_add=1, rows=self.rows if self._rows_ahead else None)
+        common = dict(W2_copy=self.W2snap, x_scale=1.0 / 255.0, keep_prob=cfg.keep_prob,
+                      seed=cfg.seed * 2654435761 + self.rank, step=A, ctr_dst=Bc, ctr_src=A,
+                      ctr_add=1)
+        if self.batch_ahead:
+            ops.mlp_fwd_logits(self.train_x, self.W1, self.b1, self.Hbuf, self.W2, self.logits2,
+                               xa=self.xa, xa_parity=parity, **common)
+        else:
+            ops.mlp_fwd_logits(self.train_x, self.W1, self.b1, self.Hbuf, self.W2, self.logits2,
+                               xb=self.xb, labels=self.train_y, yb=self.yb, idx=self.perm,
+                               cursor=A, batch=B, **common)
 
     def _launch_wgrad(self, adam: bool, commit: bool = False, parity: int = -1):
         """Softmax-xent recomputed per workgroup from the logits; dW1 (dz via the W2 snapshot and
         the H mask) and dW2 in one launch. With ``adam`` the update is the epilogue (and A = B is
         committed), else the grads go to the flat all-reduce bucket."""
         cfg, B, A, Bc = self.cfg, self.cfg.batch, self.ctrA, self.ctrB
-        # the batch rows/labels published by the forward: no gather chain in the backward
+        # the batch rows/labels published by the forward (or, batch ahead, by the previous
+        # backward): no gather chain in the backward
         common = dict(x_scales=[1.0 / 255.0, 1.0], gather=[False, False], head_modes=[2, 1],
                       head_w2=[self.W2snap, None], head_h=[self.Hbuf, None],
                       head_keep_prob=cfg.keep_prob, head_logits2=self.logits2, head_step=Bc,
                       head_step_off=-1, head_b2=self.b2, head_labels=self.yb,
                       head_loss_scale=1.0 / B, head_loss_acc=self.loss_hist,
                       head_correct_acc=self.corr_hist,
-                      next_rows=self.rows if self._rows_ahead else None,
-                      next_rows_perm=self.perm if self._rows_ahead else None,
                       head_parity=parity)
         xs, dzs = [self.xb, self.Hbuf], [None, None]
+        if self.batch_ahead:
+            xs[0] = self.xa
+            common.update(head_labels=self.ya, next_x=self.train_x, next_labels=self.train_y,
+                          next_perm=self.perm, next_xa=self.xa, next_ya=self.ya)
         if self._x_from_dataset:
             # gather the batch rows from the (never written) dataset instead of the forward's
             # freshly published copy: the rows sit in this XCD's L2 from the forward's own reads
@@ -324,7 +350,7 @@ class FusedMLPTrainer:
         # warm up on a side stream (allocator / collective communicators initialised outside
         # capture), then restore the state so warm-up steps do not count as training.
         state = (self.P, self.M, self.V, self.ctrA, self.ctrB, self.logits2, self.rows,
-                 self.loss_hist, self.corr_hist)
+                 self.loss_hist, self.corr_hist, self.xa, self.ya)
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -381,7 +407,7 @@ class FusedMLPTrainer:
         """DP step in three parts: 0 = compute up to the grad bucket, 1 = all_reduce, 2 = Adam."""
         cfg, A, Bc = self.cfg, self.ctrA, self.ctrB
         if part == 0:
-            self._launch_fwd_head()
+            self._launch_fwd_head(parity)
             self._launch_wgrad(adam=False, parity=parity)
         elif part == 1:
             if self.xgmi is not None:
@@ -402,6 +428,10 @@ class FusedMLPTrainer:
     def train_steps(self, n: int):
         """Run n steps (graph replays where possible). Reshuffles at epoch boundaries."""
         spe = self.steps_per_epoch
+        if self.batch_ahead and self._ahead_step != self.steps_done and n > 0:
+            # state restored by attribute from outside (steps_done, perm, counters): xa / ya were
+            # prepared for another step
+            self._sync_rows()
         while n > 0:
             to_epoch_end = spe - (self.steps_done % spe)
             chunk = min(n, to_epoch_end)
@@ -427,6 +457,7 @@ class FusedMLPTrainer:
                 chunk -= done
                 n -= done
                 self.steps_done += done
+                self._ahead_step = self.steps_done   # the backward published the next batch
             if self.steps_done % spe == 0:
                 self._reshuffle()
         heartbeat.beat(self.steps_done)  # progress for the runtime's hang detection

@@ -47,18 +47,21 @@ def mlp_fwd_logits(x: Tensor, W1: Tensor, b1: Tensor, H: Tensor, W2: Tensor, log
                    idx: Optional[Tensor] = None, cursor: Optional[Tensor] = None, batch: int = 0,
                    keep_prob: float = 1.0, seed: int = 0, step: Optional[Tensor] = None,
                    ctr_dst: Optional[Tensor] = None, ctr_src: Optional[Tensor] = None,
-                   ctr_add: int = 0, rows: Optional[Tensor] = None) -> None:
+                   ctr_add: int = 0, xa: Optional[Tensor] = None, xa_parity: int = -1) -> None:
     """H = dropout(relu(x·W1ᵀ+b1)) and logits2[step & 1] += H·W2ᵀ in ONE launch.
 
     ``logits2`` is [2, M, C]; the consuming wgrad (head mode) zeroes the other buffer each step.
     With ``xb``/``labels``/``yb`` the gathered u8 batch rows and their labels are published for the
     backward kernel (so it skips the cursor -> permutation -> row dependency chain).
-    ``rows`` (optional): this step's dataset rows, as the previous ``wgrad_grouped`` wrote them
-    with ``next_rows`` -- must equal ``idx[(cursor * batch + r) % len]``.
+    ``xa`` (uint8 [2, M, K], instead of ``idx``/``cursor`` and ``xb``/``yb``): this step's batch
+    sits in ``xa[step & 1]``, where the previous ``wgrad_grouped`` published it (``next_xa``), so
+    the kernel loads its X rows from an address known at launch. ``xa_parity`` 0/1 names the half
+    at launch (it must equal the step counter's parity); -1 takes it from ``step`` in-kernel.
+    Training-step kernel only: uint8 ``x`` (for its shape), K <= 1024, ``ctr_src is step``.
     """
     _impl(H).mlp_fwd_logits(x, float(x_scale), idx, cursor, int(batch), W1, b1, H,
                             float(keep_prob), int(seed), step, W2, W2_copy, logits2, xb, labels, yb,
-                            ctr_dst, ctr_src, int(ctr_add), rows)
+                            ctr_dst, ctr_src, int(ctr_add), xa, int(xa_parity))
 
 
 def wgrad_grouped(xs: Sequence[Tensor], dzs: Sequence[Optional[Tensor]], outW: Sequence[Tensor],
@@ -76,8 +79,9 @@ def wgrad_grouped(xs: Sequence[Tensor], dzs: Sequence[Optional[Tensor]], outW: S
                   weight_decay: float = 0.0, t_step: Optional[Tensor] = None,
                   grad_scale: float = 1.0, tf_style: bool = False,
                   ctr_dst: Optional[Tensor] = None, ctr_src: Optional[Tensor] = None,
-                  ctr_add: int = 0, next_rows: Optional[Tensor] = None,
-                  next_rows_perm: Optional[Tensor] = None, head_parity: int = -1) -> None:
+                  ctr_add: int = 0, head_parity: int = -1, next_x: Optional[Tensor] = None,
+                  next_labels: Optional[Tensor] = None, next_perm: Optional[Tensor] = None,
+                  next_xa: Optional[Tensor] = None, next_ya: Optional[Tensor] = None) -> None:
     """dW_i = dz_iᵀ·gather(x_i), db_i = Σ_rows dz_i for up to 2 layers in one launch.
 
     Head modes (fused MLP step): every workgroup recomputes softmax-xent from ``head_logits2``
@@ -85,6 +89,10 @@ def wgrad_grouped(xs: Sequence[Tensor], dzs: Sequence[Optional[Tensor]], outW: S
     2 -> dz = (dlogits·head_w2[i]) ⊙ (head_h[i] > 0) / head_keep_prob (hidden layer).
     ``head_parity`` 0/1 names this step's logits buffer at launch (it must equal the counter's
     parity); -1 derives it from ``head_step`` in-kernel.
+    Batch ahead: with ``next_xa`` (uint8 [2, M, K]) / ``next_ya`` (int32 [2, M]) extra workgroups
+    copy the NEXT step's batch -- rows ``next_x[p]``, labels ``next_labels[p]`` for ``p =
+    next_perm[((step + 1) * M + r) % len]`` -- into half ``(step + 1) & 1``. A 3-D ``xs[i]``
+    [2, M, K] and 2-D ``head_labels`` [2, M] are such pairs: this step reads half ``step & 1``.
     mode 0 writes ``grad_scale * dW`` into ``outW`` (e.g. views of the flat all-reduce bucket);
     mode 1 applies Adam in place to parameters ``outW``/``outB`` with state ``mW,vW,mB,vB``.
     """
@@ -99,7 +107,7 @@ def wgrad_grouped(xs: Sequence[Tensor], dzs: Sequence[Optional[Tensor]], outW: S
         list(outW), list(outB), list(mW or none), list(vW or none), list(mB or none),
         list(vB or none), float(lr), lr_t, float(betas[0]), float(betas[1]), float(eps),
         float(weight_decay), t_step, float(grad_scale), bool(tf_style), ctr_dst, ctr_src,
-        int(ctr_add), next_rows, next_rows_perm, int(head_parity))
+        int(ctr_add), next_xa, next_ya, int(head_parity), next_x, next_labels, next_perm)
 
 
 def adam_flat(P: Tensor, M: Tensor, V: Tensor, G: Tensor, *, lr: float = 1e-3,

@@ -76,6 +76,8 @@ struct ArenaWGradProblem {
   float* pW; float* mW; float* vW;  // mode 1
   float* pB; float* mB; float* vB;
   int tiles_k, tiles_n, block_begin;
+  int x_par_stride;       // bytes between the two halves of a step-parity double buffer: the rows
+                          // come from half (step & 1) of x (head modes only); 0: x is one buffer
 };
 
 // Softmax-cross-entropy head recomputed inside every wgrad workgroup from the raw logits that the
@@ -92,10 +94,16 @@ struct ArenaHead {
   int C;
   ArenaRowSource lab;       // labels (same gather as the layer input)
   float loss_scale;         // 1/batch (mean loss)
+  int lab_par_stride;       // labels between the halves of a step-parity double buffer, 0: none
   float* loss_acc; int* correct_acc; int hist_len;  // metric ring (block 0), power of two
-  // optional: the NEXT step's dataset rows, nr_out[r] = nr_perm[((step + 1) * nr_batch + r) %
-  // nr_len], written by the head block so the next forward skips the cursor -> permutation hop
-  const int* nr_perm; long long nr_len; int nr_batch; int* nr_out;
+  // optional (batch ahead): extra workgroups of the launch copy the NEXT step's batch, the u8 rows
+  // na_x[p][0 .. na_K) and labels na_lab[p] of p = na_perm[((step + 1) * na_batch + r) % na_len],
+  // into half (step + 1) & 1 of na_xa [2][na_batch][na_K] / na_ya [2][na_batch], so the next
+  // forward loads its X rows from an address it knows at launch
+  const int* na_perm; long long na_len; int na_batch;
+  const uint8_t* na_x; int na_ld, na_K;
+  const void* na_lab; int na_lab_dtype;   // dtype codes of ArenaRowSource
+  uint8_t* na_xa; int* na_ya;
 };
 
 
@@ -224,7 +232,8 @@ hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float*
                                 int M, int N, int K, float keep_prob, uint32_t seed,
                                 const long long* step_src, const float* W2, float* W2_copy, int C,
                                 float* logits2, uint8_t* xb, const void* lab_ptr, int lab_dtype,
-                                int* yb, ArenaCounterOp ctr, const int* rows, hipStream_t stream);
+                                int* yb, ArenaCounterOp ctr, const uint8_t* xa, int xa_parity,
+                                hipStream_t stream);
 hipError_t arena_xent_head(const float* H, int M, int D, const float* W2, const float* b2, int C,
                            ArenaRowSource lab, float* dlogits, float* dZ, float keep_prob,
                            int relu_mask, float loss_scale, float* loss_acc, int* correct_acc,

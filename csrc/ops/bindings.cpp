@@ -129,7 +129,10 @@ void linear_fwd(Tensor x, double x_scale, OptT idx, OptT cursor, int64_t batch, 
 void mlp_fwd_logits(Tensor x, double x_scale, OptT idx, OptT cursor, int64_t batch, Tensor W1,
                     Tensor b1, Tensor H, double keep_prob, int64_t seed, OptT step, Tensor W2,
                     OptT W2_copy, Tensor logits2, OptT xb, OptT labels, OptT yb, OptT ctr_dst,
-                    OptT ctr_src, int64_t ctr_add, OptT rows) {
+                    OptT ctr_src, int64_t ctr_add, OptT xa, py::args extra) {
+  // extra: (xa_parity,), optional -- callers from before the published batch pass 21 arguments
+  TORCH_CHECK(extra.size() <= 1, "mlp_fwd_logits: at most one argument (xa_parity) after xa");
+  const int64_t xa_parity = extra.size() == 1 ? extra[0].cast<int64_t>() : -1;
   for (auto* t : {&W1, &b1, &H, &W2, &logits2}) check_f32(*t, "mlp_fwd_logits operand");
   const int64_t M = H.size(0), N = H.size(1), K = W1.size(1), C = W2.size(0);
   TORCH_CHECK(W1.dim() == 2 && W1.size(0) == N && x.dim() == 2 && x.size(1) == K,
@@ -175,19 +178,27 @@ void mlp_fwd_logits(Tensor x, double x_scale, OptT idx, OptT cursor, int64_t bat
     lab_dtype = dtype_code(*labels);
   }
   ArenaRowSource s = make_src(x, x_scale, idx, cursor, batch, M, "x");
-  const int* prows = nullptr;
-  if (rows.has_value()) {  // this step's dataset rows (each must index x)
-    check_dev(*rows, "rows");
-    TORCH_CHECK(rows->scalar_type() == torch::kInt32 && rows->numel() == M,
-                "rows must be int32 [M]");
-    TORCH_CHECK(idx.has_value(), "rows replaces the idx/cursor gather: pass idx too");
-    prows = rows->data_ptr<int>();
+  const uint8_t* pxa = nullptr;
+  if (xa.has_value()) {  // this step's batch, published by the previous wgrad_grouped
+    check_dev(*xa, "xa");
+    TORCH_CHECK(xa->scalar_type() == torch::kUInt8 && xa->dim() == 3 && xa->size(0) == 2 &&
+                    xa->size(1) == M && xa->size(2) == K,
+                "xa must be uint8 [2, M, K]");
+    TORCH_CHECK(xa_parity >= -1 && xa_parity <= 1, "xa_parity must be -1 (from the counter), 0 or 1");
+    TORCH_CHECK(!xb.has_value() && !idx.has_value(),
+                "xa replaces the idx/cursor gather and the xb/yb publication: pass neither");
+    TORCH_CHECK(x.scalar_type() == torch::kUInt8 && K <= 1024 && step.has_value() &&
+                    ctr.dst != nullptr && ctr.src == opt_i64_scalar(step, "step"),
+                "mlp_fwd_logits: xa (the published batch) is read only by the training-step "
+                "kernel: uint8 x, K <= 1024 (got K = ", K, "), step given and ctr_src == step; "
+                "use the idx/cursor gather otherwise");
+    pxa = xa->data_ptr<uint8_t>();
   }
   check_hip(arena_mlp_fwd_logits(s, W1.data_ptr<float>(), b1.data_ptr<float>(),
                                  H.data_ptr<float>(), (int)M, (int)N, (int)K, (float)keep_prob,
                                  (uint32_t)seed, opt_i64_scalar(step, "step"), W2.data_ptr<float>(),
                                  w2c, (int)C, logits2.data_ptr<float>(), pxb, plab, lab_dtype, pyb,
-                                 ctr, prows, cur_stream()),
+                                 ctr, pxa, (int)xa_parity, cur_stream()),
             "mlp_fwd_logits");
 }
 
@@ -275,7 +286,16 @@ void wgrad_grouped(std::vector<Tensor> xs, std::vector<double> x_scales, std::ve
                    std::vector<OptT> vW, std::vector<OptT> mB, std::vector<OptT> vB, double lr,
                    OptT lr_t, double b1, double b2, double eps, double wd, OptT t_step,
                    double grad_scale, bool tf_style, OptT ctr_dst, OptT ctr_src, int64_t ctr_add,
-                   OptT next_rows, OptT next_rows_perm, int64_t hd_parity) {
+                   OptT next_xa, OptT next_ya, int64_t hd_parity, py::args extra) {
+  // extra: (next_x, next_labels, next_perm), given together with next_xa / next_ya
+  TORCH_CHECK(extra.size() == 0 || extra.size() == 3,
+              "wgrad_grouped: after hd_parity either nothing or next_x, next_labels, next_perm");
+  OptT next_x, next_labels, next_perm;
+  if (extra.size() == 3) {
+    if (!extra[0].is_none()) next_x = extra[0].cast<Tensor>();
+    if (!extra[1].is_none()) next_labels = extra[1].cast<Tensor>();
+    if (!extra[2].is_none()) next_perm = extra[2].cast<Tensor>();
+  }
   const size_t n = xs.size();
   TORCH_CHECK(hd_parity >= -1 && hd_parity <= 1, "hd_parity must be -1 (from the counter), 0 or 1");
   TORCH_CHECK(n >= 1 && n <= 2, "wgrad_grouped: 1..2 problems");
@@ -329,12 +349,23 @@ void wgrad_grouped(std::vector<Tensor> xs, std::vector<double> x_scales, std::ve
       TORCH_CHECK(hd_keep_prob > 0.0 && hd_keep_prob <= 1.0, "hd_keep_prob in (0, 1]");
       P.hd_inv_keep = (float)(1.0 / hd_keep_prob);
     }
-    const int64_t K = x.size(1);
+    // a 3-D x [2, M, K] is a step-parity double buffer (the batch published one step ahead):
+    // this step's rows are half (step & 1)
+    const bool x_pair = x.dim() == 3;
+    if (x_pair) {
+      TORCH_CHECK(x.size(0) == 2 && x.size(1) == M && hd_modes[i] != 0 && !gather[i] &&
+                      x.is_contiguous(),
+                  "a 3-D x must be a contiguous [2, M, K] parity pair of a head-mode problem");
+    }
+    const int64_t K = x.size(-1);
     TORCH_CHECK(K % 4 == 0, "wgrad: K must be a multiple of 4");
     TORCH_CHECK(x.scalar_type() == torch::kFloat32 || x.scalar_type() == torch::kUInt8,
                 "x must be f32/u8");
     P.x = gather[i] ? make_src(x, x_scales[i], idx, cursor, batch, M, "x", cursor_off)
-                    : make_src(x, x_scales[i], c10::nullopt, c10::nullopt, 0, M, "x");
+                    : make_src(x_pair ? x.select(0, 0) : x, x_scales[i], c10::nullopt,
+                               c10::nullopt, 0, M, "x");
+    TORCH_CHECK(!x_pair || M * K * (int64_t)x.element_size() < (1LL << 31), "x pair too large");
+    P.x_par_stride = x_pair ? (int)(M * K * (int64_t)x.element_size()) : 0;
     P.xt = x.scalar_type() == torch::kUInt8 ? 1 : 0;
     P.M = (int)M; P.K = (int)K; P.N = (int)N;
     P.mode = (int)mode;
@@ -390,13 +421,24 @@ void wgrad_grouped(std::vector<Tensor> xs, std::vector<double> x_scales, std::ve
       head.b2 = hd_b2->data_ptr<float>();
     }
     const int64_t Mh = hd_logits2->size(1);
-    TORCH_CHECK(hd_labels->dim() == 1 && hd_labels->scalar_type() != torch::kFloat32, "labels");
+    // 2-D labels [2, M] int32: the parity pair that goes with a 3-D x
+    const bool lab_pair = hd_labels->dim() == 2;
+    if (lab_pair) {
+      TORCH_CHECK(hd_labels->size(0) == 2 && hd_labels->size(1) == Mh &&
+                      hd_labels->scalar_type() == torch::kInt32 && hd_labels->is_contiguous(),
+                  "2-D labels must be a contiguous int32 [2, M] parity pair");
+    } else {
+      TORCH_CHECK(hd_labels->dim() == 1 && hd_labels->scalar_type() != torch::kFloat32, "labels");
+    }
     // labels share the layer-input gather (first problem with gather=True), same cursor offset
     int gi = -1;
     for (size_t i = 0; i < n; ++i)
       if (gather[i]) { gi = (int)i; break; }
+    TORCH_CHECK(!(lab_pair && gi >= 0), "a label parity pair is not gathered");
     head.lab = gi >= 0 ? make_src(*hd_labels, 1.0, idx, cursor, batch, Mh, "labels", cursor_off)
-                       : make_src(*hd_labels, 1.0, c10::nullopt, c10::nullopt, 0, Mh, "labels");
+                       : make_src(lab_pair ? hd_labels->select(0, 0) : *hd_labels, 1.0,
+                                  c10::nullopt, c10::nullopt, 0, Mh, "labels");
+    head.lab_par_stride = lab_pair ? (int)Mh : 0;
     head.loss_scale = (float)hd_loss_scale;
     check_f32(*hd_loss_acc, "hd_loss_acc");
     check_dev(*hd_correct_acc, "hd_correct_acc");
@@ -408,20 +450,43 @@ void wgrad_grouped(std::vector<Tensor> xs, std::vector<double> x_scales, std::ve
     head.loss_acc = hd_loss_acc->data_ptr<float>();
     head.correct_acc = hd_correct_acc->data_ptr<int>();
     head.hist_len = (int)hd_loss_acc->numel();
-    if (next_rows.has_value()) {
-      TORCH_CHECK(next_rows_perm.has_value(), "next_rows needs next_rows_perm");
-      check_dev(*next_rows, "next_rows");
-      check_dev(*next_rows_perm, "next_rows_perm");
-      TORCH_CHECK(next_rows->scalar_type() == torch::kInt32 &&
-                      next_rows_perm->scalar_type() == torch::kInt32,
-                  "next_rows / next_rows_perm must be int32");
-      TORCH_CHECK(next_rows->numel() <= 256 && next_rows->numel() <= next_rows_perm->numel(),
-                  "next_rows: at most 256 rows, not more than the permutation");
-      head.nr_out = next_rows->data_ptr<int>();
-      head.nr_perm = next_rows_perm->data_ptr<int>();
-      head.nr_len = next_rows_perm->numel();
-      head.nr_batch = (int)next_rows->numel();
+    if (next_xa.has_value()) {  // publish the next step's batch (ArenaHead::na_*)
+      TORCH_CHECK(next_x.has_value() && next_labels.has_value() && next_perm.has_value() &&
+                      next_ya.has_value(),
+                  "next_xa needs next_x, next_labels, next_perm and next_ya");
+      for (auto* t : {&next_x, &next_labels, &next_perm, &next_xa, &next_ya})
+        check_dev(**t, "next batch operand");
+      const int64_t Kn = next_x->dim() == 2 ? next_x->size(1) : 0, rows = next_x->size(0);
+      TORCH_CHECK(next_x->scalar_type() == torch::kUInt8 && next_x->dim() == 2 && Kn % 4 == 0 &&
+                      next_x->is_contiguous(),
+                  "next_x must be contiguous uint8 [rows, K], K % 4 == 0");
+      TORCH_CHECK(next_xa->scalar_type() == torch::kUInt8 && next_xa->dim() == 3 &&
+                      next_xa->size(0) == 2 && next_xa->size(1) == Mh && next_xa->size(2) == Kn &&
+                      next_xa->is_contiguous(),
+                  "next_xa must be contiguous uint8 [2, M, K]");
+      TORCH_CHECK(next_ya->scalar_type() == torch::kInt32 && next_ya->dim() == 2 &&
+                      next_ya->size(0) == 2 && next_ya->size(1) == Mh && next_ya->is_contiguous(),
+                  "next_ya must be contiguous int32 [2, M]");
+      TORCH_CHECK(next_labels->dim() == 1 && next_labels->size(0) >= rows &&
+                      next_labels->scalar_type() != torch::kFloat32 && next_labels->is_contiguous(),
+                  "next_labels must be integer [rows of next_x]");
+      TORCH_CHECK(next_perm->scalar_type() == torch::kInt32 && next_perm->is_contiguous() &&
+                      next_perm->numel() >= Mh,
+                  "next_perm must be int32 with at least M entries");
+      // (as for idx: its values were checked against the dataset when it was installed)
+      head.na_perm = next_perm->data_ptr<int>();
+      head.na_len = next_perm->numel();
+      head.na_batch = (int)Mh;
+      head.na_x = next_x->data_ptr<uint8_t>();
+      head.na_ld = (int)Kn;
+      head.na_K = (int)Kn;
+      head.na_lab = next_labels->data_ptr();
+      head.na_lab_dtype = dtype_code(*next_labels);
+      head.na_xa = next_xa->data_ptr<uint8_t>();
+      head.na_ya = next_ya->data_ptr<int>();
     }
+  } else {
+    TORCH_CHECK(!next_xa.has_value(), "next_xa needs a head-mode problem");
   }
   check_hip(arena_wgrad_grouped(probs.data(), (int)n, a, (float)grad_scale, ctr, head,
                                 cur_stream()),

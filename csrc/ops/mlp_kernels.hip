@@ -18,6 +18,7 @@
 #include "adam.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 using namespace arena;
@@ -328,6 +329,12 @@ struct WGradArgs {
   ArenaCounterOp ctr;
   ArenaHead head;    // used by problems with hd_mode != 0
   int head_block;    // first block of the first head-mode problem: zeroes + records metrics
+  int pub_begin;     // first of the blocks that publish the next step's batch (INT_MAX: none)
+  // p[i].x_par_stride as the kernel reads it (0 once the launcher has applied a launch-time
+  // parity); kept apart from p[i] so the prologue's loads of tiles / block_begin stay as they were
+  int x_par_stride[kMaxProblems];
+  int first_block[kMaxProblems];  // p[i].block_begin again, next to pub_begin: the role split
+                                  // reads one run of kernel arguments
 };
 
 constexpr int kMC = 128;       // rows per LDS chunk
@@ -346,8 +353,9 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 template <int XT>
-__device__ __forceinline__ void load_x_items(const ArenaWGradProblem& P, const Gather& gt, int mc0,
-                                             int mcn, int k0, float4 (&v)[kXItems]) {
+__device__ __forceinline__ void load_x_items(const ArenaWGradProblem& P, const ArenaRowSource& xs,
+                                             const Gather& gt, int mc0, int mcn, int k0,
+                                             float4 (&v)[kXItems]) {
   // 16 items per row, item q = 4 consecutive k (one u32 of u8 pixels or one float4). Rows past
   // mcn re-read row mcn-1 (finite data; their A operand is zeroed in the K-loop).
   int prow[kXItems];
@@ -360,7 +368,7 @@ __device__ __forceinline__ void load_x_items(const ArenaWGradProblem& P, const G
   for (int i = 0; i < kXItems; ++i) {
     const int q = (threadIdx.x + 256 * i) & 15;
     float f[4];
-    load4<XT>(P.x, prow[i], min(k0 + 4 * q, P.K - 4), f);
+    load4<XT>(xs, prow[i], min(k0 + 4 * q, P.K - 4), f);
     v[i] = make_float4(f[0], f[1], f[2], f[3]);
   }
 }
@@ -382,10 +390,55 @@ __device__ __forceinline__ void store_f4_wt(float* p, const float4& v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
 }
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_u4_wt(void* p, const u32x4& v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void store_u1_wt(void* p, uint32_t v) {
+  asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+
 __device__ __forceinline__ int load_label(const ArenaRowSource& lab, long long pr) {
   if (lab.dtype == 1) return (int)static_cast<const uint8_t*>(lab.ptr)[pr];
   if (lab.dtype == 2) return static_cast<const int*>(lab.ptr)[pr];
   return (int)static_cast<const long long*>(lab.ptr)[pr];
+}
+
+// The publishing role of a head-mode launch (ArenaHead::na_*): the blocks from pub_begin on copy
+// the NEXT step's batch into the half of xa / ya that no block of this launch reads. One wave per
+// row, four rows per block: step counter -> permutation -> row bytes -> write-through stores
+// (nothing left dirty for the end-of-kernel release). The position formula is make_gather's; the
+// wrap may fall inside the batch. Bounds: r < na_batch, q < na_len (na_batch <= na_len, host-
+// checked), the permutation's values index na_x (checked when it is installed), k < na_K.
+__device__ __forceinline__ void publish_next_batch(const ArenaHead& HD, int first_row) {
+  const int r = first_row + wave_id();
+  if (r >= HD.na_batch) return;
+  const int lane = lane_id();
+  ARENA_TL(1, 0);
+  const long long nstep = *HD.step + HD.step_off + 1;
+  long long q = mod_fp64((double)nstep * (double)HD.na_batch, HD.na_len) + r;
+  q = (q >= HD.na_len) ? q - HD.na_len : q;
+  const long long prow = HD.na_perm[q];
+  const int K = HD.na_K;
+  const long long slot = (nstep & 1) * HD.na_batch + r;
+  const uint8_t* src = HD.na_x + prow * HD.na_ld;
+  uint8_t* dst = HD.na_xa + slot * K;
+  if (lane == 0) {
+    const int y = (HD.na_lab_dtype == 1) ? (int)static_cast<const uint8_t*>(HD.na_lab)[prow]
+                : (HD.na_lab_dtype == 2) ? static_cast<const int*>(HD.na_lab)[prow]
+                                         : (int)static_cast<const long long*>(HD.na_lab)[prow];
+    store_u1_wt(HD.na_ya + slot, (uint32_t)y);
+  }
+  if ((((uintptr_t)HD.na_x | (uintptr_t)HD.na_xa | (uintptr_t)HD.na_ld | (uintptr_t)K) & 15) == 0) {
+    for (int k = 16 * lane; k < K; k += 16 * 64)
+      store_u4_wt(dst + k, *reinterpret_cast<const u32x4*>(src + k));
+  } else {  // K % 4 == 0 and 4-byte-aligned rows (host-checked)
+    for (int k = 4 * lane; k < K; k += 4 * 64)
+      store_u1_wt(dst + k, *reinterpret_cast<const uint32_t*>(src + k));
+  }
+  ARENA_TL(1, 6);
+  ARENA_TL_DRAIN();
+  ARENA_TL(1, 7);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -401,6 +454,8 @@ __device__ __forceinline__ int load_label(const ArenaRowSource& lab, long long p
 //                    the two 16-lane groups of each half-wave hit disjoint banks)
 //   D              : lane l, reg r -> dW[n0 + 4(l>>4) + r][k0 + 16w + (l&15)]   (coalesced rows)
 // >= 2 waves/SIMD so all 424 workgroups x 4 waves are co-resident in ONE round on 1024 SIMDs.
+// The 25 publishing workgroups of the MNIST step (publish_next_batch) ride in the same round:
+// 449 blocks at 58.9 KB of LDS each are two per CU on 225 of 256 CUs; nothing waits on them.
 // ---------------------------------------------------------------------------------------------
 // Per-problem compile-time specialisation. SPEC == 0: every property of the problem is read at run
 // time (generic path). Otherwise SPEC - 1 = xt | hd_mode << 1 | gather << 3 | mode << 4 |
@@ -485,6 +540,17 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
   }
   const float* logits = nullptr;
   long long hstep = 0;
+  // Step-parity double buffers of X and the labels (the batch published one step ahead): with the
+  // parity known at launch the host has moved the pointers already (strides 0 here); otherwise
+  // the half is chosen by the step counter, which the X loads then wait for.
+  ArenaRowSource xsrc = P.x, labsrc = HD.lab;
+  if constexpr (!WS::sp) {
+    if (hmode != 0 && (args.x_par_stride[pi] != 0 || HD.lab_par_stride != 0)) {
+      const long long par = (hstep_raw + HD.step_off) & 1;
+      xsrc.ptr = static_cast<const char*>(P.x.ptr) + par * (long long)args.x_par_stride[pi];
+      labsrc.ptr = static_cast<const int*>(HD.lab.ptr) + par * HD.lab_par_stride;
+    }
+  }
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   f32x4 accb = {0.f, 0.f, 0.f, 0.f};
@@ -507,9 +573,9 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
 #pragma unroll
       for (int i = 0; i < kXItems; ++i) xv[i] = make_float4(0.5f, 0.25f, 0.f, 1.f);
     } else if (xt == 1) {
-      load_x_items<1>(P, gt, mc0, mcn, k0, xv);
+      load_x_items<1>(P, xsrc, gt, mc0, mcn, k0, xv);
     } else {
-      load_x_items<0>(P, gt, mc0, mcn, k0, xv);
+      load_x_items<0>(P, xsrc, gt, mc0, mcn, k0, xv);
     }
     ARENA_TL(1, 8);
     float4 zv[kZItems];
@@ -536,9 +602,9 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
         // labels share the layer input's gather (same rows); no gather -> direct
         const Gather lg = (LG == 0) ? Gather{nullptr, 0, P.M} : make_gather(HD.lab);
         const long long pr = gather_row(lg, mc0 + min((int)threadIdx.x, mcn - 1));
-        if constexpr (LDT == 1) yv = static_cast<const uint8_t*>(HD.lab.ptr)[pr];
-        else if constexpr (LDT == 2) yv = static_cast<const int*>(HD.lab.ptr)[pr];
-        else yv = load_label(HD.lab, pr);
+        if constexpr (LDT == 1) yv = static_cast<const uint8_t*>(labsrc.ptr)[pr];
+        else if constexpr (LDT == 2) yv = static_cast<const int*>(labsrc.ptr)[pr];
+        else yv = load_label(labsrc, pr);
       }
       {
         const float* b2p = HD.b2 ? HD.b2 : P.hd_w2 ? P.hd_w2 : HD.logits2;  // any valid address
@@ -583,12 +649,6 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
         if constexpr (WS::sp) hstep = hstep_raw + HD.step_off;  // this block only waits here
         float* nxt = HD.logits2 + (long long)((hstep + 1) & 1) * P.M * HD.C;
         for (int i = threadIdx.x; i < P.M * HD.C; i += 256) nxt[i] = 0.f;
-        if (HD.nr_out != nullptr && (int)threadIdx.x < HD.nr_batch) {
-          long long q = mod_fp64((double)(hstep + 1) * (double)HD.nr_batch, HD.nr_len) +
-                        (long long)threadIdx.x;
-          q = (q >= HD.nr_len) ? q - HD.nr_len : q;
-          HD.nr_out[threadIdx.x] = HD.nr_perm[q];
-        }
         if (threadIdx.x == 0 && HD.hist_len > 1) {
           const int ns = (int)(hstep + 1) & (HD.hist_len - 1);
           HD.loss_acc[ns] = 0.f;
@@ -876,14 +936,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   int pi = 0;
 #pragma unroll
   for (int i = 1; i < kMaxProblems; ++i)
-    if (i < args.nprob && (int)blockIdx.x >= args.p[i].block_begin) pi = i;
+    if (i < args.nprob && (int)blockIdx.x >= args.first_block[i]) pi = i;
   if constexpr (S0 != 0 && S1 != 0) {
     // the head's labels follow problem 0's gather (the binding shares it with the label source)
     // (published batch: int32 labels; dataset gather: the dataset's uint8 labels)
     constexpr int LG = WSpec<S0>::gather;
     constexpr int LDT = LG ? 1 : 2;
+    // Third role, behind the last problem's blocks: the next step's batch (no LDS, no barrier).
+    // Tested after the problem split on purpose: a test ahead of it makes the kernel-argument
+    // loads of the 424 tile blocks wait behind one more scalar round trip (measured: + 0.36 us
+    // on the launch).
     if (pi == 0) wgrad_body<CB, S0, LG, LDT>(args, 0, Xs, Zs, Ds, W2s, Ys, B2s);
+    else if ((int)blockIdx.x >= args.pub_begin)
+      publish_next_batch(args.head, 4 * ((int)blockIdx.x - args.pub_begin));
     else wgrad_body<CB, S1, LG, LDT>(args, 1, Xs, Zs, Ds, W2s, Ys, B2s);
+  } else if ((int)blockIdx.x >= args.pub_begin) {
+    publish_next_batch(args.head, 4 * ((int)blockIdx.x - args.pub_begin));
   } else {
     wgrad_body<CB, 0, -1, -1>(args, pi, Xs, Zs, Ds, W2s, Ys, B2s);
   }
@@ -899,15 +967,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 // m-tile-0 workgroups also snapshot W2 for the backward pass (which updates W2 in place). The
 // softmax itself is recomputed by every wgrad workgroup: no intra-kernel hand-off anywhere.
 // ---------------------------------------------------------------------------------------------
-// FM: 0 = generic; 1 = training-step fast path gathering rows from the step counter; 2 = fast
-// path reading this step's rows precomputed by the previous backward kernel.
+// FM: 0 = generic; 1 = training-step fast path gathering rows from the step counter; 2 / 3 = fast
+// path reading this step's batch from xa, where the previous backward kernel published it (2: xa
+// is the half of this step's parity, chosen at launch; 3: xa is the pair, the half comes from the
+// step counter).
 template <int XT, int WAVES, int FM>
 __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
     ArenaRowSource src, const float* __restrict__ W, const float* __restrict__ bias,
     float* __restrict__ Y, int M, int N, int K, uint32_t keep_thr, float inv_keep, uint32_t seed,
     const long long* step_src, const float* __restrict__ W2, float* __restrict__ W2_copy, int C,
     float* __restrict__ logits2, uint8_t* __restrict__ xb, const void* __restrict__ lab_ptr,
-    int lab_dtype, int* __restrict__ yb, ArenaCounterOp ctr, const int* __restrict__ rows) {
+    int lab_dtype, int* __restrict__ yb, ArenaCounterOp ctr, const uint8_t* __restrict__ xa) {
   constexpr int CH = 8;
   const int lane = lane_id(), w = wave_id();
   const int g = lane >> 4, c = lane & 15;
@@ -935,13 +1005,21 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
     // the cursor -> index -> row chain, whose waits leave the W loads in flight. The counter is
     // kept lane-varying (opaque zero) so hipcc does not drain it into an SGPR at once, and the
     // label publication and the counter update move to the end.
+    // FM 2 / 3 (host-checked: counter-op source == step counter, one K chunk per wave): the X rows
+    // sit at an address known at launch, so their loads go out with the W loads and nothing waits
+    // for the counter before the K-loop (FM 3 waits for it once, for the parity; no index hop).
     int lz;
     asm volatile("v_mov_b32 %0, 0" : "=v"(lz));
-    // FM 2: the row index is the oldest load, so waiting for it leaves the W loads in flight
-    int prow2 = 0;
-    if constexpr (FM == 2) prow2 = rows[rowc] + lz;
     const int A = *reinterpret_cast<const int*>(step_src) + lz;
     __builtin_amdgcn_sched_barrier(0);
+    uint32_t raw[CH];
+    if constexpr (FM >= 2) {
+      static_assert(FM < 2 || XT == 1, "the published batch is uint8");
+      const uint8_t* xrow = xa + ((FM == 3 ? (long long)(A & 1) * M : 0LL) + rowc) * (long long)K;
+#pragma unroll
+      for (int i = 0; i < CH; ++i)
+        raw[i] = *reinterpret_cast<const uint32_t*>(xrow + min((s0 + i) * 16 + 4 * g, K - 4));
+    }
     float b[CH][4];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
@@ -953,24 +1031,25 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
              min(n0 + ((int)threadIdx.x & 15), N - 1)];
     bv = bias[min(n0 + ((int)threadIdx.x & 15), N - 1)];
     __builtin_amdgcn_sched_barrier(0);  // keep the independent loads above the counter's first use
-    if constexpr (FM == 2) {  // this step's rows, precomputed by the previous backward kernel
-      prow = prow2;
-    } else {
+    if constexpr (FM == 1) {
       long long p = mod_fp64((double)A * (double)src.batch, src.idx_len) + rowc;
       p = (p >= src.idx_len) ? p - src.idx_len : p;
       prow = src.idx[p];
+      ARENA_TL_DEP((int)prow);
+    } else {
+      prow = 0;
+      ARENA_TL_DEP((int)raw[0]);
     }
     stepv = A;
-    ARENA_TL_DEP((int)prow);
     ARENA_TL(0, 1);
     float a[CH][4];
-    uint32_t raw[CH];
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int kc = min((s0 + i) * 16 + 4 * g, K - 4);
       if constexpr (XT == 1) {
-        raw[i] = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src.ptr) +
-                                                    prow * (long long)src.ld + kc);
+        if constexpr (FM == 1)
+          raw[i] = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(src.ptr) +
+                                                      prow * (long long)src.ld + kc);
 #pragma unroll
         for (int j = 0; j < 4; ++j) a[i][j] = (float)((raw[i] >> (8 * j)) & 0xffu) * src.scale;
       } else {
@@ -978,7 +1057,7 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
         raw[i] = 0;
       }
     }
-    if constexpr (XT == 1) {
+    if constexpr (XT == 1 && FM == 1) {
       if (publish && m0 + c < M) {
 #pragma unroll
         for (int i = 0; i < CH; ++i) {
@@ -1106,7 +1185,7 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
     }
   }
   if constexpr (FAST) {
-    if (publish && w == 0 && g == 0 && m0 + c < M) {
+    if (FM == 1 && publish && w == 0 && g == 0 && m0 + c < M) {
       const int y = (lab_dtype == 1) ? (int)static_cast<const uint8_t*>(lab_ptr)[prow]
                   : (lab_dtype == 2) ? static_cast<const int*>(lab_ptr)[prow]
                                      : (int)static_cast<const long long*>(lab_ptr)[prow];
@@ -1747,7 +1826,8 @@ hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float*
                                 int M, int N, int K, float keep_prob, uint32_t seed,
                                 const long long* step_src, const float* W2, float* W2_copy, int C,
                                 float* logits2, uint8_t* xb, const void* lab_ptr, int lab_dtype,
-                                int* yb, ArenaCounterOp ctr, const int* rows, hipStream_t stream) {
+                                int* yb, ArenaCounterOp ctr, const uint8_t* xa, int xa_parity,
+                                hipStream_t stream) {
   if (C < 1 || C > 16 || K % 4) return hipErrorInvalidValue;
   uint32_t thr = 0xFFFFFFFFu;
   float inv_keep = 1.f;
@@ -1758,18 +1838,27 @@ hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float*
   dim3 grid((N + 15) / 16, (M + 15) / 16);
   // the training step's configuration gets the straight-line variant (see the kernel)
   const int nsteps = (K + 15) / 16;
-  const bool fast = src.dtype == 1 && src.idx != nullptr && src.cursor != nullptr &&
-                    src.cursor == step_src && src.cursor_off == 0 && ctr.dst != nullptr &&
-                    ctr.src == step_src && xb != nullptr && lab_ptr != nullptr &&
-                    (nsteps + 7) / 8 <= 8 && src.idx_len < (1LL << 31);
-  if (fast && rows != nullptr)
-    hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 2>), grid, dim3(512), 0, stream, src, W,
-                       bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
-                       xb, lab_ptr, lab_dtype, yb, ctr, rows);
-  else if (fast)
+  const bool step_fast = src.dtype == 1 && step_src != nullptr && ctr.dst != nullptr &&
+                         ctr.src == step_src && (nsteps + 7) / 8 <= 8;
+  const bool fast = step_fast && src.idx != nullptr && src.cursor == step_src &&
+                    src.cursor_off == 0 && xb != nullptr && lab_ptr != nullptr &&
+                    src.idx_len < (1LL << 31);
+  if (xa != nullptr) {
+    // the batch published by the previous wgrad_grouped: xa [2][M][K] uint8, half = step parity.
+    // Only the straight-line variant reads it (the binding refuses other shapes with a message).
+    if (!step_fast || xa_parity < -1 || xa_parity > 1) return hipErrorInvalidValue;
+    if (xa_parity >= 0)
+      hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 2>), grid, dim3(512), 0, stream, src, W,
+                         bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
+                         nullptr, nullptr, 0, nullptr, ctr, xa + (size_t)xa_parity * M * K);
+    else
+      hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 3>), grid, dim3(512), 0, stream, src, W,
+                         bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
+                         nullptr, nullptr, 0, nullptr, ctr, xa);
+  } else if (fast)
     hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 1>), grid, dim3(512), 0, stream, src, W,
                        bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
-                       xb, lab_ptr, lab_dtype, yb, ctr, rows);
+                       xb, lab_ptr, lab_dtype, yb, ctr, nullptr);
   else if (src.dtype == 1)
     hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 0>), grid, dim3(512), 0, stream, src, W,
                        bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
@@ -1832,16 +1921,42 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
   a.grad_scale = grad_scale;
   a.ctr = ctr;
   a.head = head;
+  a.pub_begin = INT_MAX;
+  int pub_blocks = 0;
+  if (head.na_xa != nullptr) {  // the next step's batch: one wave per row behind the tile blocks
+    if (a.head_block < 0 || !head.step || !head.na_perm || !head.na_x || !head.na_lab ||
+        !head.na_ya || head.na_batch < 1 || head.na_batch > head.na_len || head.na_K % 4 ||
+        head.na_ld % 4 || head.na_K > head.na_ld)
+      return hipErrorInvalidValue;
+    a.pub_begin = blocks;
+    pub_blocks = (head.na_batch + 3) / 4;
+  }
+  const bool sp = head.parity == 0 || head.parity == 1;
+  if (head.lab_par_stride != 0 && head.lab.dtype != 2) return hipErrorInvalidValue;
+  for (int i = 0; i < nprob; ++i)
+    if (probs[i].x_par_stride != 0 && probs[i].hd_mode == 0) return hipErrorInvalidValue;
+  if (sp) {  // parity known at launch: point at this step's halves, nothing left for the kernel
+    for (int i = 0; i < nprob; ++i) {
+      a.p[i].x.ptr = static_cast<const char*>(a.p[i].x.ptr) +
+                     (long long)head.parity * a.p[i].x_par_stride;
+      a.p[i].x_par_stride = 0;
+    }
+    a.head.lab.ptr = static_cast<const int*>(head.lab.ptr) + head.parity * head.lab_par_stride;
+    a.head.lab_par_stride = 0;
+  }
+  for (int i = 0; i < kMaxProblems; ++i) {
+    a.x_par_stride[i] = i < nprob ? a.p[i].x_par_stride : 0;
+    a.first_block[i] = i < nprob ? a.p[i].block_begin : INT_MAX;
+  }
   // the fused MLP step: problem 0 = u8 dataset rows + hidden head, problem 1 = f32 H + output head
   const bool g0 = probs[0].x.idx != nullptr;
-  const bool sp = head.parity == 0 || head.parity == 1;
   const bool mlp_pair = nprob == 2 && head.C <= 10 && probs[0].xt == 1 && probs[0].hd_mode == 2 &&
                         probs[1].xt == 0 && probs[1].hd_mode == 1 && probs[1].x.idx == nullptr &&
                         probs[0].mode == probs[1].mode && probs[0].M <= kMC &&
                         (probs[0].mode == 0 || (adam.t_ptr && adam.lr_ptr)) && head.step &&
                         probs[1].M <= kMC && head.lab.dtype == (g0 ? 1 : 2) &&
                         wgrad_vec_ok(probs[0]) && wgrad_vec_ok(probs[1]);
-  const dim3 grid(blocks), block(256);
+  const dim3 grid(blocks + pub_blocks), block(256);
   if (mlp_pair) {
     const int m = probs[0].mode & 1;
 #define ARENA_WG_PAIR(G, M, SP)                                                                \

@@ -73,6 +73,19 @@ def main():
     wg, w0, w1 = analyse(tl, 1, 424)
     res = {"fwd": fwd, "wgrad": wg, "fwd_end_to_wgrad_start_us": round(w0 - f1, 3),
            "step_span_us": round(w1 - f0, 3)}
+    if getattr(tr, "batch_ahead", False):
+        # the blocks behind the 424 tile blocks publish the next step's batch: entry (0), stores
+        # issued (6), drained (7), against the tile blocks' first start and last end
+        nb = (tr.cfg.batch + 3) // 4
+        t = tl[1, 424:424 + nb].double() * 10.0 / 1000.0
+        t = t[t[:, 0] > 0]
+        res["publish"] = {"blocks": int(t.shape[0]),
+                          "first_entry_us": round(float(t[:, 0].min()) - w0, 3),
+                          "med_entry_to_stores_issued_us":
+                              round(float((t[:, 6] - t[:, 0]).median()), 3),
+                          "med_own_span_us": round(float((t[:, 7] - t[:, 0]).median()), 3),
+                          "last_store_drained_us": round(float(t[:, 7].max()) - w0, 3),
+                          "tile_blocks_end_us": round(w1 - w0, 3)}
     print(json.dumps(res, indent=1))
 
 
