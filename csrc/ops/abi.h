@@ -314,6 +314,11 @@ void arena_bn_set_pool_quad_mult(int m);
 void arena_bn_set_acc_max_pairs(long long p);
 long long arena_bn_acc_max_pairs();
 int arena_bn_acc_ok(long long M, int C);
+// read-only views of the host-side path selection (tests assert the path a shape takes):
+// row blocks of a reduction over M x C and their rows per block (0 for an unsupported shape);
+// level-1 finalize blocks per channel group for nblk partials
+long long arena_bn_reduce_blocks(long long M, int C, long long* rpb);
+int arena_bn_fin_blocks(long long nblk);
 void arena_bn_set_reduce_geometry(long long max_blocks, long long min_rounds);
 long long arena_bn_lvl2_doubles(long long nblk, int C);
 long long arena_bn_workspace_floats(long long M, int C);

@@ -2404,6 +2404,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_set_nt", [](int64_t on) { arena_bn_set_nt((int)on); });
   m.def("bn_set_pool_quad_mult", [](int64_t m) { arena_bn_set_pool_quad_mult((int)m); });
   m.def("bn_set_acc", [](bool on) { g_bn_acc = on; });
+  // read-only: the path a shape takes under the current switches
+  m.def("bn_reduce_blocks", [](int64_t M, int64_t C) {
+    long long rpb = 0;
+    const long long nblk = arena_bn_reduce_blocks(M, (int)C, &rpb);
+    return std::make_pair((int64_t)nblk, (int64_t)rpb);
+  });
+  m.def("bn_fin_blocks", [](int64_t nblk) { return (int64_t)arena_bn_fin_blocks(nblk); });
+  m.def("bn_acc_ok", [](int64_t M, int64_t C) { return arena_bn_acc_ok(M, (int)C) != 0; });
   m.def("bn_acc_scratch", [](bool on) { g_acc_scratch = on; });
   m.def("bn_pool_fwd", &bn_pool_fwd);
   m.attr("acc_rep") = (int)ARENA_ACC_REP;   // replicas per BatchNorm accumulator set

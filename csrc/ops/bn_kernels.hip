@@ -868,16 +868,17 @@ __global__ __launch_bounds__(kT) void bn_bwd_dx_kernel(const T* __restrict__ dy,
     }
     __syncthreads();
     const int cgl = cs / kVec;
-    if ((int)threadIdx.x < cs) {
-      const int gq = threadIdx.x / kVec, i = threadIdx.x % kVec;
+    // (a flat grid covers all C channels: more than kT of them for C > 256)
+    for (int cl = threadIdx.x; cl < cs; cl += kT) {
+      const int gq = cl / kVec, i = cl % kVec;
       float a = 0.f, b = 0.f;
       for (int r = 0; r < kT / cgl; ++r) {
         a += s_a2[(r * cgl + gq) * kVec + i];
         b += s_b2[(r * cgl + gq) * kVec + i];
       }
       double* dst = acc2 + (size_t)(blockIdx.x % kAccRep) * 2 * C;
-      unsafeAtomicAdd(dst + q.c_lo + threadIdx.x, (double)a);
-      unsafeAtomicAdd(dst + C + q.c_lo + threadIdx.x, (double)b);
+      unsafeAtomicAdd(dst + q.c_lo + cl, (double)a);
+      unsafeAtomicAdd(dst + C + q.c_lo + cl, (double)b);
     }
   }
 }
@@ -1509,6 +1510,14 @@ int arena_bn_acc_ok(long long M, int C) {
   return reduce_blocks(M, C, &rpb) * C <= g_acc_max_pairs ? 1 : 0;
 }
 
+long long arena_bn_reduce_blocks(long long M, int C, long long* rpb) {
+  *rpb = 0;
+  if (bad_shape(M, C)) return 0;
+  return reduce_blocks(M, C, rpb);
+}
+
+int arena_bn_fin_blocks(long long nblk) { return fin_blocks_per_group((int)nblk); }
+
 void arena_bn_set_reduce_geometry(long long max_blocks, long long min_rounds) {
   g_max_reduce_blocks = max_blocks < 1 ? 1 : (max_blocks > 4096 ? 4096 : max_blocks);
   g_min_rounds = min_rounds < 1 ? 1 : min_rounds;
@@ -1719,7 +1728,9 @@ hipError_t arena_bn_pool_fwd(int dtype, const void* x, void* y, uint8_t* pos, vo
                              unsigned* tickets, double* zero, int nzero, hipStream_t stream) {
   PoolG g{N, H, W, C, (H + 2 * p - k) / s + 1, (W + 2 * p - k) / s + 1, k, s, p};
   const long long M = (long long)N * H * W;
-  if (bad_shape(M, C) || C > 256 || (k + s - 1) / s != 2 || 2 * p > k || g.OH <= 0 || g.OW <= 0)
+  // (H + 2p < k: the C division above rounds a negative quotient towards zero, OH would be 1)
+  if (bad_shape(M, C) || C > 256 || (k + s - 1) / s != 2 || 2 * p > k || H + 2 * p < k ||
+      W + 2 * p < k || g.OH <= 0 || g.OW <= 0)
     return hipErrorInvalidValue;
   if (fin == nullptr) {
     if (part == nullptr || ext_nblk <= 0 || ext_rpb <= 0 || (long long)ext_nblk * ext_rpb < M ||
@@ -1754,7 +1765,8 @@ hipError_t arena_bn_pool_bwd(int dtype, const void* dy, const uint8_t* pos, cons
   PoolG g{N, H, W, C, (H + 2 * p - k) / s + 1, (W + 2 * p - k) / s + 1, k, s, p};
   const long long M = (long long)N * H * W;
   if (bad_shape(M, C) || C > 256 || M >= (1LL << 31) || acc == nullptr || co.scale == nullptr ||
-      co.shift == nullptr || (k + s - 1) / s != 2 || 2 * p > k || g.OH <= 0 || g.OW <= 0)
+      co.shift == nullptr || (k + s - 1) / s != 2 || 2 * p > k || H + 2 * p < k ||
+      W + 2 * p < k || g.OH <= 0 || g.OW <= 0)
     return hipErrorInvalidValue;
   // up to 4x the usual reduction grid: the stem's C = 64 leaves 512 row blocks latency-bound
   // on their gathers, and 2048 x 64 sums are still few atomics
