@@ -242,6 +242,7 @@ hipError_t arena_xent_head(const float* H, int M, int D, const float* W2, const 
 hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam adam,
                                float grad_scale, ArenaCounterOp ctr, ArenaHead head,
                                hipStream_t stream);
+void arena_wgrad_short_images(int on);
 hipError_t arena_adam_flat(float* P, float* M, float* V, const float* G, long long n,
                            ArenaAdam adam, ArenaCounterOp ctr, hipStream_t stream);
 hipError_t arena_sgd_flat(float* P, const float* G, long long n, float lr, const float* lr_ptr,

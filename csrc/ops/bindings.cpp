@@ -2424,6 +2424,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("xent_head", &xent_head);
   m.def("mlp_fwd_logits", &mlp_fwd_logits);
   m.def("wgrad_grouped", &wgrad_grouped);
+  // A/B and test switch: False keeps 128-row LDS images in the MNIST step's compiled backward
+  // pair for every batch size (default True: 112 rows when the batch has at most 112)
+  m.def("wgrad_short_images", [](bool on) { arena_wgrad_short_images(on ? 1 : 0); });
   m.def("adam_flat", &adam_flat);
   m.def("sgd_flat", &sgd_flat);
   m.def("softmax_xent", &softmax_xent);

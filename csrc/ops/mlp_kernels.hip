@@ -338,6 +338,7 @@ struct WGradArgs {
 };
 
 constexpr int kMC = 128;       // rows per LDS chunk
+constexpr int kMCShort = 112;  // ... of the MNIST step's compiled pair when M <= 112 (its M is 100)
 constexpr int kXsStride = 80;  // floats
 constexpr int kXItems = (kMC * 16) / 256;  // X staging items per thread (16 per row)
 constexpr int kZItems = (kMC * 4) / 256;   // dZ staging items per thread (4 float4 per row)
@@ -352,20 +353,20 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-template <int XT>
+template <int XT, int XI>
 __device__ __forceinline__ void load_x_items(const ArenaWGradProblem& P, const ArenaRowSource& xs,
                                              const Gather& gt, int mc0, int mcn, int k0,
-                                             float4 (&v)[kXItems]) {
+                                             float4 (&v)[XI]) {
   // 16 items per row, item q = 4 consecutive k (one u32 of u8 pixels or one float4). Rows past
   // mcn re-read row mcn-1 (finite data; their A operand is zeroed in the K-loop).
-  int prow[kXItems];
+  int prow[XI];
 #pragma unroll
-  for (int i = 0; i < kXItems; ++i) {
+  for (int i = 0; i < XI; ++i) {
     const int t = threadIdx.x + 256 * i;
     prow[i] = gather_row(gt, mc0 + min(t >> 4, mcn - 1));
   }
 #pragma unroll
-  for (int i = 0; i < kXItems; ++i) {
+  for (int i = 0; i < XI; ++i) {
     const int q = (threadIdx.x + 256 * i) & 15;
     float f[4];
     load4<XT>(xs, prow[i], min(k0 + 4 * q, P.K - 4), f);
@@ -476,13 +477,19 @@ constexpr int wgrad_spec(int xt, int hm, int gather, int mode, int sp = 0) {
   return 1 + xt + 2 * hm + 8 * gather + 16 * mode + 32 * sp;
 }
 
-template <int CB, int SPEC, int LG, int LDT>  // CB: bound on head classes (C <= CB); LG: labels
-                                              // gathered, LDT: label dtype (-1: run time)
+template <int CB, int SPEC, int LG, int LDT, int MC>  // CB: bound on head classes (C <= CB); LG:
+                                              // labels gathered, LDT: label dtype (-1: run time),
+                                              // MC: rows of the LDS images that are staged and
+                                              // multiplied (kMC, or kMCShort on the spec path when
+                                              // M fits: no all-padding items, no all-zero steps)
 // (LDS images come in as plain pointers: __restrict__ here would let hipcc move LDS accesses
 // across the raw s_barrier in lds_barrier(), whose memory clobber noalias memory escapes)
 __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float* Xs, float* Zs,
                                            float* Ds, float* W2s, int* Ys, float* B2s) {
   using WS = WSpec<SPEC>;
+  constexpr int XI = (MC * 16) / 256, DI = (MC * 16) / 256;  // X / logits staging items per thread
+  static_assert(MC == kMC || WS::known, "short LDS images: spec path only (one chunk, M <= MC)");
+  static_assert(MC % 16 == 0 && MC <= kMC && MC > kMC / 2, "K-loop: whole groups of 16 rows");
   const ArenaWGradProblem& P = args.p[pi];
   const ArenaHead& HD = args.head;
   const int local = blockIdx.x - P.block_begin;
@@ -563,23 +570,23 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
   const int vn = n0 + ((int)threadIdx.x >> 4), vk = k0 + 4 * ((int)threadIdx.x & 15);
   const bool vec = WS::known || wgrad_vec_ok(P);
   // spec path: the host guarantees M <= kMC, so the chunk loop (and every mc0 == 0 test) folds away
-  const int nchunks = WS::known ? 1 : (P.M + kMC - 1) / kMC;
+  const int nchunks = WS::known ? 1 : (P.M + MC - 1) / MC;
   for (int ci = 0; ci < nchunks; ++ci) {
-    const int mc0 = ci * kMC;
-    const int mcn = min(kMC, P.M - mc0);
+    const int mc0 = ci * MC;
+    const int mcn = min(MC, P.M - mc0);
     // (1) issue the chunk's loads
-    float4 xv[kXItems];
+    float4 xv[XI];
     if (ARENA_EXP & 2) {
 #pragma unroll
-      for (int i = 0; i < kXItems; ++i) xv[i] = make_float4(0.5f, 0.25f, 0.f, 1.f);
+      for (int i = 0; i < XI; ++i) xv[i] = make_float4(0.5f, 0.25f, 0.f, 1.f);
     } else if (xt == 1) {
-      load_x_items<1>(P, xsrc, gt, mc0, mcn, k0, xv);
+      load_x_items<1, XI>(P, xsrc, gt, mc0, mcn, k0, xv);
     } else {
-      load_x_items<0>(P, xsrc, gt, mc0, mcn, k0, xv);
+      load_x_items<0, XI>(P, xsrc, gt, mc0, mcn, k0, xv);
     }
     ARENA_TL(1, 8);
     float4 zv[kZItems];
-    float dv[kDItems];
+    float dv[DI];
     float wv = 0.f, bv = 0.f;
     int yv = 0;
     if (hmode == 0) {
@@ -598,7 +605,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
       }
     } else {
       const int C = HD.C;
-      if ((int)threadIdx.x < kMC) {
+      if ((int)threadIdx.x < MC) {
         // labels share the layer input's gather (same rows); no gather -> direct
         const Gather lg = (LG == 0) ? Gather{nullptr, 0, P.M} : make_gather(HD.lab);
         const long long pr = gather_row(lg, mc0 + min((int)threadIdx.x, mcn - 1));
@@ -639,7 +646,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
         }
       }
 #pragma unroll
-      for (int i = 0; i < kDItems; ++i) {  // raw logits rows: item t -> (m = t>>4, c = t&15)
+      for (int i = 0; i < DI; ++i) {  // raw logits rows: item t -> (m = t>>4, c = t&15)
         const int t = threadIdx.x + 256 * i;
         if (ARENA_EXP & 1) dv[i] = 0.01f * (float)(t & 15);
         else dv[i] = logits[(long long)(mc0 + min(t >> 4, mcn - 1)) * C + min(t & 15, C - 1)];
@@ -691,7 +698,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
     }
     // (3) LDS images; every store unconditional (no branch for hipcc to sink a load into)
 #pragma unroll
-    for (int i = 0; i < kXItems; ++i) {
+    for (int i = 0; i < XI; ++i) {
       const int t = threadIdx.x + 256 * i;
       const int rr = t >> 4, q = t & 15;
       const float4 o = (k0 + 4 * q < P.K) ? xv[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -714,8 +721,8 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
     } else {
       const int C = HD.C;
 #pragma unroll
-      for (int i = 0; i < kDItems; ++i) Ds[threadIdx.x + 256 * i] = dv[i];
-      if ((int)threadIdx.x < kMC) Ys[threadIdx.x] = yv;
+      for (int i = 0; i < DI; ++i) Ds[threadIdx.x + 256 * i] = dv[i];
+      if ((int)threadIdx.x < MC) Ys[threadIdx.x] = yv;
       if (threadIdx.x < 16) B2s[threadIdx.x] = bv;
       W2s[threadIdx.x] = (((int)threadIdx.x >> 4) < C) ? wv : 0.f;
       lds_barrier();
@@ -796,16 +803,16 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
     }
     lds_barrier();
     ARENA_TL(1, 4);
-    // (4) K-loop over all kMC rows of the image (rows >= mcn: Zs zero, Xs finite). Four
+    // (4) K-loop over all MC rows of the image (rows >= mcn: Zs zero, Xs finite). Four
     //     independent accumulator chains (the f32 MFMA's dependent latency is 40 cycles, its
     //     issue 8): a quarter of the serial depth. Bias columns (db = dZᵀ·1) run in the same
     //     loop in the k-tile-0 blocks only (a block-uniform branch outside the loop).
-    if (mcn > kMC / 2) {
+    if (mcn > kMC / 2) {  // (kMC whatever MC is: the same sum order as the 128-row images)
       f32x4 ch[4] = {acc, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       if (tk == 0) {
         f32x4 chb[4] = {accb, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-        for (int s = 0; s < kMC / 4; s += 4) {
+        for (int s = 0; s < MC / 4; s += 4) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int m = 4 * (s + j) + g;
@@ -818,7 +825,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
         accb = (chb[0] + chb[1]) + (chb[2] + chb[3]);
       } else {
 #pragma unroll
-        for (int s = 0; s < kMC / 4; s += 4) {
+        for (int s = 0; s < MC / 4; s += 4) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int m = 4 * (s + j) + g;
@@ -923,7 +930,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
 }
 
 // S0 / S1: specs of problems 0 / 1 (both nonzero = the fused MLP step's fixed pair; 0 = generic).
-template <int CB, int S0, int S1>
+template <int CB, int S0, int S1, int MC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void wgrad_grouped_kernel(
     WGradArgs args) {
   __shared__ __attribute__((aligned(16))) float Xs[kMC * kXsStride];
@@ -946,14 +953,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     // Tested after the problem split on purpose: a test ahead of it makes the kernel-argument
     // loads of the 424 tile blocks wait behind one more scalar round trip (measured: + 0.36 us
     // on the launch).
-    if (pi == 0) wgrad_body<CB, S0, LG, LDT>(args, 0, Xs, Zs, Ds, W2s, Ys, B2s);
+    if (pi == 0) wgrad_body<CB, S0, LG, LDT, MC>(args, 0, Xs, Zs, Ds, W2s, Ys, B2s);
     else if ((int)blockIdx.x >= args.pub_begin)
       publish_next_batch(args.head, 4 * ((int)blockIdx.x - args.pub_begin));
-    else wgrad_body<CB, S1, LG, LDT>(args, 1, Xs, Zs, Ds, W2s, Ys, B2s);
+    else wgrad_body<CB, S1, LG, LDT, MC>(args, 1, Xs, Zs, Ds, W2s, Ys, B2s);
   } else if ((int)blockIdx.x >= args.pub_begin) {
     publish_next_batch(args.head, 4 * ((int)blockIdx.x - args.pub_begin));
   } else {
-    wgrad_body<CB, 0, -1, -1>(args, pi, Xs, Zs, Ds, W2s, Ys, B2s);
+    wgrad_body<CB, 0, -1, -1, kMC>(args, pi, Xs, Zs, Ds, W2s, Ys, B2s);
   }
   counter_op(args.ctr);  // A = B last: nothing in this kernel reads A
 }
@@ -1900,6 +1907,10 @@ hipError_t arena_xent_head(const float* H, int M, int D, const float* W2, const 
   return hipGetLastError();
 }
 
+// Process-wide switch for A/Bs and tests: off keeps kMC-row LDS images for every batch size.
+static bool g_wgrad_short_images = true;
+void arena_wgrad_short_images(int on) { g_wgrad_short_images = on != 0; }
+
 hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam adam,
                                float grad_scale, ArenaCounterOp ctr, ArenaHead head,
                                hipStream_t stream) {
@@ -1959,9 +1970,20 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
   const dim3 grid(blocks + pub_blocks), block(256);
   if (mlp_pair) {
     const int m = probs[0].mode & 1;
-#define ARENA_WG_PAIR(G, M, SP)                                                                \
+    const bool short_mc = g_wgrad_short_images && probs[0].M <= kMCShort &&
+                          probs[1].M <= kMCShort;
+#define ARENA_WG_PAIR_MC(G, M, SP, MC)                                                         \
   hipLaunchKernelGGL((wgrad_grouped_kernel<10, wgrad_spec(1, 2, G, M, SP),                     \
-                                           wgrad_spec(0, 1, 0, M, SP)>), grid, block, 0, stream, a)
+                                           wgrad_spec(0, 1, 0, M, SP), MC>), grid, block, 0,   \
+                     stream, a)
+  // kMCShort rows when the batch fits: no staging item that holds only padding rows, no K-loop
+  // step that multiplies only zeros (docs/perf.md, "Logits accumulators: one copy per group of
+  // n-tiles", which kept this part)
+#define ARENA_WG_PAIR(G, M, SP)                         \
+  do {                                                  \
+    if (short_mc) ARENA_WG_PAIR_MC(G, M, SP, kMCShort); \
+    else ARENA_WG_PAIR_MC(G, M, SP, kMC);               \
+  } while (0)
     if (sp) {
       if (g0 == 0 && m == 0) ARENA_WG_PAIR(0, 0, 1);
       else if (g0 == 0 && m == 1) ARENA_WG_PAIR(0, 1, 1);
@@ -1974,10 +1996,11 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
       else ARENA_WG_PAIR(1, 1, 0);
     }
 #undef ARENA_WG_PAIR
+#undef ARENA_WG_PAIR_MC
   } else if (head.C <= 10) {
-    hipLaunchKernelGGL((wgrad_grouped_kernel<10, 0, 0>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((wgrad_grouped_kernel<10, 0, 0, kMC>), grid, block, 0, stream, a);
   } else {
-    hipLaunchKernelGGL((wgrad_grouped_kernel<16, 0, 0>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((wgrad_grouped_kernel<16, 0, 0, kMC>), grid, block, 0, stream, a);
   }
   return hipGetLastError();
 }
