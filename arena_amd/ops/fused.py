@@ -158,8 +158,9 @@ def mt_sgd_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tenso
                   wbf: Tensor, *, lr: float, momentum: float, weight_decay: float,
                   lr_t: Optional[Tensor] = None) -> None:
     """One launch (per 48 tensors) of momentum SGD over bf16 grads with fp32 master weights;
-    also writes the rounded bf16 weights into ``wbf`` (see ``mt_sgd_master_kernel``). ``lr_t``
-    (optional, fp32 [1]) is read by the kernel instead of ``lr``: a schedule under graph replay."""
+    also writes the rounded bf16 weights into ``wbf`` (``mt_master_kernel<SgdRule>`` in
+    ``csrc/ops/optim_kernels.hip``). ``lr_t`` (optional, fp32 [1]) is read by the kernel instead
+    of ``lr``: a schedule under graph replay."""
     _impl(master).mt_sgd_master(list(grads), [int(o) for o in offsets], master, mom, wbf,
                                 float(lr), float(momentum), float(weight_decay),
                                 lr_t=_check_lr_t(lr_t, master))

@@ -4,7 +4,7 @@
 and their fp32 master copies + momentum in flat fp32 buffers. The bf16 weights feed the MFMA
 convolutions directly, so a bf16-autocast step has no per-weight fp32->bf16 cast in the forward
 and no bf16->fp32 gradient cast in the backward; the update is one multi-tensor kernel
-(``mt_sgd_master`` in ``csrc/ops/mlp_kernels.hip``). The reference trains through TF inside its
+(``mt_sgd_master`` in ``csrc/ops/optim_kernels.hip``). The reference trains through TF inside its
 Horovod image (``charts/tf-horovod/values.yaml``); tf_cnn_benchmarks' fp16 mode keeps fp32
 master variables the same way.
 

@@ -2,7 +2,8 @@
 
 Used (a) as the numerics oracle in tests and (b) as the implementation for CPU tensors (the
 multi-process gloo paths that run without a GPU). Semantics match csrc/ops/mlp_kernels.hip
-exactly, including the counter-hash dropout mask, the device step counters and the gather.
+and csrc/ops/optim_kernels.hip exactly, including the counter-hash dropout mask, the device step
+counters and the gather.
 """
 from __future__ import annotations
 
@@ -117,7 +118,7 @@ def xent_head(H, W2, b2, labels, idx, cursor, batch, dlogits, dZ, keep_prob, rel
 
 
 def adam_update(p, m, v, g, lr, b1, b2, eps, wd, t, grad_scale, tf_style):
-    """In-place Adam on tensors (fp32), same formula as adam_apply in mlp_kernels.hip."""
+    """In-place Adam on tensors (fp32), same formula as adam_apply in csrc/ops/adam.h."""
     g = g * grad_scale + wd * p
     m.mul_(b1).add_(g, alpha=1.0 - b1)
     v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
@@ -313,8 +314,8 @@ def mt_sgd_f32(grads, offsets, w, mom, lr, momentum, weight_decay, scale, lr_t=N
 
 # ------------------------------------------------------------------------------------------------
 # RMSProp and Adam, TF1's forms (tf_cnn_benchmarks' defaults assume them: --rmsprop_epsilon 1.0
-# sits inside the square root). Defined once, here; the HIP kernels (``mt_opt_*_kernel`` in
-# csrc/ops/mlp_kernels.hip), ``TFRMSprop`` / ``TFAdam`` and the tests follow it. Both take the
+# sits inside the square root). Defined once, here; the HIP kernels (``RmspropRule`` / ``AdamRule``
+# in csrc/ops/optim_kernels.hip), ``TFRMSprop`` / ``TFAdam`` and the tests follow it. Both take the
 # coupled gradient of the SGD kernels, ``d = g * scale + wd * w`` (``scale`` only on the fp32
 # group), and every operation below is an fp32 operation in the order written:
 #
@@ -421,7 +422,7 @@ def mt_adam_f32(grads, offsets, w, m, v, corr, lr, b1, omb1, b2, omb2, eps, weig
 # ------------------------------------------------------------------------------------------------
 # LARS (layer-wise adaptive rate scaling), tf.contrib's LARSOptimizer as the MLPerf ResNet
 # reference uses it: momentum SGD whose learning rate is scaled per tensor. Defined once, here; the
-# HIP kernels (``mt_lars_*_kernel`` in csrc/ops/mlp_kernels.hip), ``MasterLARS`` / ``TFLars`` and
+# HIP kernels (``mt_lars_*_kernel`` in csrc/ops/optim_kernels.hip), ``MasterLARS`` / ``TFLars`` and
 # the tests follow it. For a tensor with fp32 master w, bf16 gradient g and momentum m:
 #
 #       wn = ||w||2            gn = ||g||2

@@ -2,7 +2,7 @@
 
 A captured hipGraph bakes a ``float`` kernel argument in, so a schedule cannot reach the update
 kernels as a host value. Here the learning rate is one fp32 value in device memory
-(:class:`DeviceLR`): a one-lane kernel (``arena_lr_schedule`` in ``csrc/ops/mlp_kernels.hip``)
+(:class:`DeviceLR`): a one-lane kernel (``arena_lr_schedule`` in ``csrc/ops/optim_kernels.hip``)
 at the head of every step evaluates the schedule at the device step counter, writes the value and
 counts the step; every SGD update kernel reads it through its ``lr_ptr`` argument.
 

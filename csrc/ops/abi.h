@@ -58,6 +58,20 @@ struct ArenaAdam {
   int tf_style;           // 1: TF AdamOptimizer epsilon placement, 0: torch.optim.Adam
 };
 
+// The multi-tensor optimizer updates (csrc/ops/optim_kernels.hip): which rule, and its numbers.
+// RMSProp and Adam are TF1's forms (arena_amd/ops/reference.py defines them); 1 - rho / 1 - b1 /
+// 1 - b2 are formed in fp64 by the caller: the fp32 difference 1 - float(0.999) is 4.7e-5 off.
+enum { ARENA_OPT_SGD = 0, ARENA_OPT_RMSPROP = 1, ARENA_OPT_ADAM = 2 };
+struct ArenaOptHyper {
+  float lr;             // replaced by *lr_ptr when that is set
+  const float* lr_ptr;  // device learning rate (DeviceLR), or null
+  const float* corr;    // Adam: the clock's sqrt(1 - b2^t) / (1 - b1^t); the others: null
+  float a, oma;         // RMSProp: rho, 1 - rho;  Adam: b1, 1 - b1;  LARS: eeta, unused
+  float b, omb;         // SGD, LARS, RMSProp: momentum, unused;      Adam: b2, 1 - b2
+  float eps, wd;        // RMSProp, Adam, LARS: their epsilon (SGD: unused); weight decay
+  float scale;          // gradient scale (fp32 layout and shard_sgd; the master layout has none)
+};
+
 // One layer of a grouped weight-gradient launch (wgrad_grouped).
 struct ArenaWGradProblem {
   ArenaRowSource x;       // rows m of the layer input
@@ -243,49 +257,38 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
                                float grad_scale, ArenaCounterOp ctr, ArenaHead head,
                                hipStream_t stream);
 void arena_wgrad_short_images(int on);
+hipError_t arena_softmax_xent(const float* logits, const long long* labels, int M, int C,
+                              float* loss, float* dlogits, float grad_scale, hipStream_t stream);
+#ifdef ARENA_TIMELINE
+hipError_t arena_timeline_read(long long* host, int clear);
+#endif
+
+// csrc/ops/optim_kernels.hip
 hipError_t arena_adam_flat(float* P, float* M, float* V, const float* G, long long n,
                            ArenaAdam adam, ArenaCounterOp ctr, hipStream_t stream);
 hipError_t arena_sgd_flat(float* P, const float* G, long long n, float lr, const float* lr_ptr,
                           float gscale, hipStream_t stream);
-hipError_t arena_softmax_xent(const float* logits, const long long* labels, int M, int C,
-                              float* loss, float* dlogits, float grad_scale, hipStream_t stream);
 hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const long long* ns,
                                int count, float* flat, float scale, int dir, hipStream_t stream);
-hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, const long long* ns,
-                               int count, float* master, float* mom, void* wbf, float lr,
-                               const float* lr_ptr, float mu, float wd, hipStream_t stream);
+// Multi-tensor updates by `rule` (ARENA_OPT_*, hyper: ArenaOptHyper's column for it), one launch
+// per 48 tensors; gradient i updates [offs[i], offs[i] + ns[i]) of the flat buffers. st0 / st1: the
+// rule's fp32 state buffers (SGD keeps one: st1 is not touched).
+//   _master: bf16 gradients, fp32 masters and states, rounded bf16 weights to wbf (offs / ns
+//            multiples of 4); no gradient scale.
+//   _f32:    fp32 tensors and gradients, any sizes and offsets.
+hipError_t arena_mt_update_master(int rule, const void* const* grads, const long long* offs,
+                                  const long long* ns, int count, float* master, float* st0,
+                                  float* st1, void* wbf, ArenaOptHyper hyper, hipStream_t stream);
+hipError_t arena_mt_update_f32(int rule, const float* const* grads, const long long* offs,
+                               const long long* ns, int count, float* w, float* st0, float* st1,
+                               ArenaOptHyper hyper, hipStream_t stream);
 hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
                            long long n, float lr, const float* lr_ptr, float mu, float wd,
                            float scale, hipStream_t stream);
-// fp32 multi-tensor momentum SGD: gradient i updates w/mom[offs[i], offs[i] + ns[i]) (any sizes).
-hipError_t arena_mt_sgd_f32(const float* const* grads, const long long* offs, const long long* ns,
-                            int count, float* w, float* mom, float lr, const float* lr_ptr,
-                            float mu, float wd, float scale, hipStream_t stream);
 // lr[0] = value of the piecewise-linear schedule seg[n_seg][4] (begin, end, lr0 bits, lr1 bits;
 // fp64 values as int64 bit patterns) at *step, then *step += 1.
 hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
                              hipStream_t stream);
-// RMSProp / Adam (TF1 forms, arena_amd/ops/reference.py) as multi-tensor updates. *_master: bf16
-// gradients, fp32 masters and two fp32 state buffers, rounded bf16 weights to wbf (offs / ns
-// multiples of 4); *_f32: fp32 tensors and gradients, any sizes. omr / omb1 / omb2 are 1 - rho /
-// 1 - b1 / 1 - b2 formed in fp64 by the caller; corr is arena_adam_tick's bias correction.
-hipError_t arena_mt_rmsprop_master(const void* const* grads, const long long* offs,
-                                   const long long* ns, int count, float* master, float* ms,
-                                   float* mom, void* wbf, float lr, const float* lr_ptr, float rho,
-                                   float omr, float mu, float eps, float wd, hipStream_t stream);
-hipError_t arena_mt_adam_master(const void* const* grads, const long long* offs,
-                                const long long* ns, int count, float* master, float* m, float* v,
-                                void* wbf, float lr, const float* lr_ptr, const float* corr,
-                                float b1, float omb1, float b2, float omb2, float eps, float wd,
-                                hipStream_t stream);
-hipError_t arena_mt_rmsprop_f32(const float* const* grads, const long long* offs,
-                                const long long* ns, int count, float* w, float* ms, float* mom,
-                                float lr, const float* lr_ptr, float rho, float omr, float mu,
-                                float eps, float wd, float scale, hipStream_t stream);
-hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, const long long* ns,
-                             int count, float* w, float* m, float* v, float lr,
-                             const float* lr_ptr, const float* corr, float b1, float omb1, float b2,
-                             float omb2, float eps, float wd, float scale, hipStream_t stream);
 // LARS (arena_amd/ops/reference.py) over bf16 gradients with fp32 masters, two launches per 48
 // tensors: per-block partial sums of w^2 and g^2 into workspace, then the update, whose blocks
 // each reduce their tensor's partials, form trust = eeta * |w| / (|g| + wd * |w| + eps) (1 when a
@@ -294,16 +297,12 @@ hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, c
 long long arena_mt_lars_workspace_floats(const long long* ns, int count);
 hipError_t arena_mt_lars_master(const void* const* grads, const long long* offs,
                                 const long long* ns, const int* slots, int count, float* master,
-                                float* mom, void* wbf, float* trust, float* workspace, float lr,
-                                const float* lr_ptr, float mu, float wd, float eeta, float eps,
-                                hipStream_t stream);
+                                float* mom, void* wbf, float* trust, float* workspace,
+                                ArenaOptHyper hyper, hipStream_t stream);
 // t = *step + 1; pw[0] *= b1; pw[1] *= b2; *corr = float(sqrt(1 - pw[1]) / (1 - pw[0])) in fp64,
 // every operation rounded on its own; *step = t.
 hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,
                            hipStream_t stream);
-#ifdef ARENA_TIMELINE
-hipError_t arena_timeline_read(long long* host, int clear);
-#endif
 
 // csrc/ops/bn_kernels.hip
 void arena_bn_set_fin_max_blocks(int p);

@@ -568,71 +568,6 @@ void mt_copy_scale(std::vector<Tensor> tensors, std::vector<int64_t> offsets, Te
             "mt_copy_scale");
 }
 
-void mt_sgd_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
-                   Tensor mom, Tensor wbf, double lr, double momentum, double weight_decay,
-                   OptT lr_t) {
-  check_f32(master, "master");
-  const float* lp = opt_lr_ptr(lr_t, master, "mt_sgd_master");
-  check_f32(mom, "mom");
-  check_dev(wbf, "wbf");
-  TORCH_CHECK(wbf.scalar_type() == torch::kBFloat16 && wbf.is_contiguous() &&
-                  mom.numel() == master.numel() && wbf.numel() == master.numel(),
-              "mt_sgd_master: flat buffers must be fp32/fp32/bf16 of equal size");
-  TORCH_CHECK(grads.size() == offsets.size(), "offsets length");
-  std::vector<const void*> ptrs;
-  std::vector<long long> offs, ns;
-  for (size_t i = 0; i < grads.size(); ++i) {
-    const Tensor& g = grads[i];
-    TORCH_CHECK(g.is_cuda() && g.device() == master.device(), "grad ", i,
-                " must be on the master buffer's GPU");
-    TORCH_CHECK(g.scalar_type() == torch::kBFloat16 && g.is_non_overlapping_and_dense(),
-                "mt_sgd_master: grad ", i, " must be dense bf16");
-    TORCH_CHECK(g.numel() % 4 == 0 && offsets[i] % 4 == 0 && offsets[i] >= 0 &&
-                    offsets[i] + g.numel() <= master.numel(),
-                "mt_sgd_master: segment ", i, " misaligned or out of bounds");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 8 == 0, "grad ", i, " not 8B aligned");
-    ptrs.push_back(g.data_ptr());
-    offs.push_back(offsets[i]);
-    ns.push_back(g.numel());
-  }
-  check_hip(arena_mt_sgd_master(ptrs.data(), offs.data(), ns.data(), (int)ptrs.size(),
-                                master.data_ptr<float>(), mom.data_ptr<float>(), wbf.data_ptr(),
-                                (float)lr, lp, (float)momentum, (float)weight_decay,
-                                cur_stream()),
-            "mt_sgd_master");
-}
-
-// Momentum SGD on fp32 tensors: gradient i updates w/mom[offsets[i], offsets[i] + numel_i).
-void mt_sgd_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor mom,
-                double lr, double momentum, double weight_decay, double scale, OptT lr_t) {
-  check_f32(w, "w");
-  check_f32(mom, "mom");
-  const float* lp = opt_lr_ptr(lr_t, w, "mt_sgd_f32");
-  TORCH_CHECK(mom.numel() == w.numel() && mom.device() == w.device(),
-              "mt_sgd_f32: w and mom must be equal-size buffers on one GPU");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(mom.data_ptr()) % 16 == 0,
-              "mt_sgd_f32: w and mom must be 16-byte aligned");
-  TORCH_CHECK(grads.size() == offsets.size(), "offsets length");
-  std::vector<const float*> ptrs;
-  std::vector<long long> offs, ns;
-  for (size_t i = 0; i < grads.size(); ++i) {
-    const Tensor& g = grads[i];
-    TORCH_CHECK(g.is_cuda() && g.device() == w.device(), "grad ", i, " must be on w's GPU");
-    TORCH_CHECK(g.scalar_type() == torch::kFloat32 && g.is_non_overlapping_and_dense(),
-                "mt_sgd_f32: grad ", i, " must be dense fp32");
-    TORCH_CHECK(offsets[i] >= 0 && offsets[i] + g.numel() <= w.numel(), "mt_sgd_f32: segment ", i,
-                " out of bounds");
-    ptrs.push_back(g.data_ptr<float>());
-    offs.push_back(offsets[i]);
-    ns.push_back(g.numel());
-  }
-  check_hip(arena_mt_sgd_f32(ptrs.data(), offs.data(), ns.data(), (int)ptrs.size(),
-                             w.data_ptr<float>(), mom.data_ptr<float>(), (float)lr, lp,
-                             (float)momentum, (float)weight_decay, (float)scale, cur_stream()),
-            "mt_sgd_f32");
-}
-
 // lr[0] = schedule(seg)(step[0]); step[0] += 1. seg: int64 [n, 4] rows (begin, end, lr0, lr1) with
 // the fp64 values as bit patterns (arena_amd/ops/schedule.py).
 void lr_schedule(Tensor seg, Tensor step, Tensor lr) {
@@ -653,34 +588,41 @@ void lr_schedule(Tensor seg, Tensor step, Tensor lr) {
             "lr_schedule");
 }
 
-// ---- RMSProp / Adam multi-tensor updates: the argument checks of mt_sgd_master / mt_sgd_f32 ----
+// ---- multi-tensor updates (SGD, RMSProp, Adam, LARS): one set of argument checks per layout ----
 struct MtSegments {
   std::vector<const void*> ptrs;
   std::vector<long long> offs, ns;
+  float* st[2] = {nullptr, nullptr};  // the rule's state buffers: one for SGD and LARS, else two
 };
 
-// master / st0 / st1 fp32 and wbf bf16, equal sizes on one GPU; bf16 gradients there, dense,
-// 8-byte aligned, sizes and offsets multiples of 4, inside the buffers.
+bool aligned_to(const Tensor& t, uintptr_t bytes) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0;
+}
+
+// Master layout. master and the rule's state buffers (one or two) fp32 and wbf bf16, equal sizes
+// on one GPU, 16-byte (wbf: 8-byte) aligned; bf16 gradients there, dense, 8-byte aligned, sizes
+// and offsets multiples of 4, inside the buffers.
 MtSegments master_segments(const std::vector<Tensor>& grads, const std::vector<int64_t>& offsets,
-                           const Tensor& master, const Tensor& st0, const Tensor& st1,
+                           const Tensor& master, const std::vector<Tensor>& states,
                            const Tensor& wbf, const char* what) {
   check_f32(master, "master");
-  check_f32(st0, "state 0");
-  check_f32(st1, "state 1");
   check_dev(wbf, "wbf");
-  TORCH_CHECK(wbf.scalar_type() == torch::kBFloat16 && st0.numel() == master.numel() &&
-                  st1.numel() == master.numel() && wbf.numel() == master.numel(),
-              what, ": flat buffers must be fp32/fp32/fp32/bf16 of equal size");
-  TORCH_CHECK(st0.device() == master.device() && st1.device() == master.device() &&
-                  wbf.device() == master.device(),
-              what, ": flat buffers must share one GPU");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(master.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(st0.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(st1.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(wbf.data_ptr()) % 8 == 0,
-              what, ": flat buffers must be 16-byte (wbf: 8-byte) aligned");
-  TORCH_CHECK(grads.size() == offsets.size(), what, ": offsets length");
+  TORCH_CHECK(wbf.scalar_type() == torch::kBFloat16 && wbf.numel() == master.numel(), what,
+              ": flat buffers must be fp32 (master, states) and bf16 (wbf) of equal size");
+  TORCH_CHECK(wbf.device() == master.device(), what, ": flat buffers must share one GPU");
+  TORCH_CHECK(aligned_to(master, 16) && aligned_to(wbf, 8), what,
+              ": flat buffers must be 16-byte (wbf: 8-byte) aligned");
+  for (const Tensor& st : states) {
+    check_f32(st, "state");
+    TORCH_CHECK(st.numel() == master.numel(), what,
+                ": flat buffers must be fp32 (master, states) and bf16 (wbf) of equal size");
+    TORCH_CHECK(st.device() == master.device(), what, ": flat buffers must share one GPU");
+    TORCH_CHECK(aligned_to(st, 16), what, ": flat buffers must be 16-byte (wbf: 8-byte) aligned");
+  }
+  TORCH_CHECK(grads.size() == offsets.size() && states.size() >= 1 && states.size() <= 2, what,
+              ": offsets length");
   MtSegments s;
+  for (size_t i = 0; i < states.size(); ++i) s.st[i] = states[i].data_ptr<float>();
   for (size_t i = 0; i < grads.size(); ++i) {
     const Tensor& g = grads[i];
     TORCH_CHECK(g.is_cuda() && g.device() == master.device(), what, ": grad ", i,
@@ -690,8 +632,7 @@ MtSegments master_segments(const std::vector<Tensor>& grads, const std::vector<i
     TORCH_CHECK(g.numel() % 4 == 0 && offsets[i] % 4 == 0 && offsets[i] >= 0 &&
                     offsets[i] + g.numel() <= master.numel(),
                 what, ": segment ", i, " misaligned or out of bounds");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 8 == 0, what, ": grad ", i,
-                " not 8B aligned");
+    TORCH_CHECK(aligned_to(g, 8), what, ": grad ", i, " not 8B aligned");
     s.ptrs.push_back(g.data_ptr());
     s.offs.push_back(offsets[i]);
     s.ns.push_back(g.numel());
@@ -699,22 +640,22 @@ MtSegments master_segments(const std::vector<Tensor>& grads, const std::vector<i
   return s;
 }
 
-// w / st0 / st1 fp32, equal sizes, 16-byte aligned, on one GPU; dense fp32 gradients there, any
-// sizes and offsets inside the buffers.
+// fp32 layout. w and the rule's state buffers (one or two) fp32, equal sizes, 16-byte aligned, on
+// one GPU; dense fp32 gradients there, any sizes and offsets inside the buffers.
 MtSegments f32_segments(const std::vector<Tensor>& grads, const std::vector<int64_t>& offsets,
-                        const Tensor& w, const Tensor& st0, const Tensor& st1, const char* what) {
+                        const Tensor& w, const std::vector<Tensor>& states, const char* what) {
   check_f32(w, "w");
-  check_f32(st0, "state 0");
-  check_f32(st1, "state 1");
-  TORCH_CHECK(st0.numel() == w.numel() && st1.numel() == w.numel() &&
-                  st0.device() == w.device() && st1.device() == w.device(),
-              what, ": w and the state buffers must be equal-size buffers on one GPU");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(st0.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(st1.data_ptr()) % 16 == 0,
-              what, ": w and the state buffers must be 16-byte aligned");
-  TORCH_CHECK(grads.size() == offsets.size(), what, ": offsets length");
+  TORCH_CHECK(aligned_to(w, 16), what, ": w and the state buffers must be 16-byte aligned");
+  for (const Tensor& st : states) {
+    check_f32(st, "state");
+    TORCH_CHECK(st.numel() == w.numel() && st.device() == w.device(), what,
+                ": w and the state buffers must be equal-size buffers on one GPU");
+    TORCH_CHECK(aligned_to(st, 16), what, ": w and the state buffers must be 16-byte aligned");
+  }
+  TORCH_CHECK(grads.size() == offsets.size() && states.size() >= 1 && states.size() <= 2, what,
+              ": offsets length");
   MtSegments s;
+  for (size_t i = 0; i < states.size(); ++i) s.st[i] = states[i].data_ptr<float>();
   for (size_t i = 0; i < grads.size(); ++i) {
     const Tensor& g = grads[i];
     TORCH_CHECK(g.is_cuda() && g.device() == w.device(), what, ": grad ", i,
@@ -738,31 +679,88 @@ const float* corr_ptr(const Tensor& corr, const Tensor& like, const char* what) 
   return corr.data_ptr<float>();
 }
 
+// What every rule shares; the caller names the rule's own fields (ArenaOptHyper's columns).
+ArenaOptHyper opt_hyper(double lr, const OptT& lr_t, const Tensor& like, double weight_decay,
+                        double scale, const char* what) {
+  ArenaOptHyper h{};
+  h.lr = (float)lr;
+  h.lr_ptr = opt_lr_ptr(lr_t, like, what);
+  h.wd = (float)weight_decay;
+  h.scale = (float)scale;
+  return h;
+}
+
+void update_master(int rule, const MtSegments& s, Tensor& master, Tensor& wbf,
+                   const ArenaOptHyper& h, const char* what) {
+  check_hip(arena_mt_update_master(rule, s.ptrs.data(), s.offs.data(), s.ns.data(),
+                                   (int)s.ptrs.size(), master.data_ptr<float>(), s.st[0], s.st[1],
+                                   wbf.data_ptr(), h, cur_stream()),
+            what);
+}
+
+void update_f32(int rule, const MtSegments& s, Tensor& w, const ArenaOptHyper& h,
+                const char* what) {
+  check_hip(arena_mt_update_f32(rule, reinterpret_cast<const float* const*>(s.ptrs.data()),
+                                s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
+                                w.data_ptr<float>(), s.st[0], s.st[1], h, cur_stream()),
+            what);
+}
+
+void mt_sgd_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
+                   Tensor mom, Tensor wbf, double lr, double momentum, double weight_decay,
+                   OptT lr_t) {
+  const MtSegments s = master_segments(grads, offsets, master, {mom}, wbf, "mt_sgd_master");
+  ArenaOptHyper h = opt_hyper(lr, lr_t, master, weight_decay, 1.0, "mt_sgd_master");
+  h.b = (float)momentum;
+  update_master(ARENA_OPT_SGD, s, master, wbf, h, "mt_sgd_master");
+}
+
+// Momentum SGD on fp32 tensors: gradient i updates w/mom[offsets[i], offsets[i] + numel_i).
+void mt_sgd_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor mom,
+                double lr, double momentum, double weight_decay, double scale, OptT lr_t) {
+  const MtSegments s = f32_segments(grads, offsets, w, {mom}, "mt_sgd_f32");
+  ArenaOptHyper h = opt_hyper(lr, lr_t, w, weight_decay, scale, "mt_sgd_f32");
+  h.b = (float)momentum;
+  update_f32(ARENA_OPT_SGD, s, w, h, "mt_sgd_f32");
+}
+
+// omr / omb1 / omb2: 1 - rho / 1 - b1 / 1 - b2, formed by the caller in fp64.
+ArenaOptHyper rmsprop_hyper(ArenaOptHyper h, double rho, double omr, double momentum, double eps) {
+  h.a = (float)rho;
+  h.oma = (float)omr;
+  h.b = (float)momentum;
+  h.eps = (float)eps;
+  return h;
+}
+
+ArenaOptHyper adam_hyper(ArenaOptHyper h, const float* corr, double b1, double omb1, double b2,
+                         double omb2, double eps) {
+  h.corr = corr;
+  h.a = (float)b1;
+  h.oma = (float)omb1;
+  h.b = (float)b2;
+  h.omb = (float)omb2;
+  h.eps = (float)eps;
+  return h;
+}
+
 void mt_rmsprop_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
                        Tensor ms, Tensor mom, Tensor wbf, double lr, double rho, double omr,
                        double momentum, double eps, double weight_decay, OptT lr_t) {
-  const MtSegments s = master_segments(grads, offsets, master, ms, mom, wbf, "mt_rmsprop_master");
-  const float* lp = opt_lr_ptr(lr_t, master, "mt_rmsprop_master");
-  check_hip(arena_mt_rmsprop_master(s.ptrs.data(), s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
-                                    master.data_ptr<float>(), ms.data_ptr<float>(),
-                                    mom.data_ptr<float>(), wbf.data_ptr(), (float)lr, lp,
-                                    (float)rho, (float)omr, (float)momentum, (float)eps,
-                                    (float)weight_decay, cur_stream()),
-            "mt_rmsprop_master");
+  const MtSegments s = master_segments(grads, offsets, master, {ms, mom}, wbf, "mt_rmsprop_master");
+  const ArenaOptHyper h = rmsprop_hyper(
+      opt_hyper(lr, lr_t, master, weight_decay, 1.0, "mt_rmsprop_master"), rho, omr, momentum, eps);
+  update_master(ARENA_OPT_RMSPROP, s, master, wbf, h, "mt_rmsprop_master");
 }
 
 void mt_adam_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
                     Tensor m, Tensor v, Tensor wbf, Tensor corr, double lr, double b1, double omb1,
                     double b2, double omb2, double eps, double weight_decay, OptT lr_t) {
-  const MtSegments s = master_segments(grads, offsets, master, m, v, wbf, "mt_adam_master");
-  const float* lp = opt_lr_ptr(lr_t, master, "mt_adam_master");
-  const float* cp = corr_ptr(corr, master, "mt_adam_master");
-  check_hip(arena_mt_adam_master(s.ptrs.data(), s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
-                                 master.data_ptr<float>(), m.data_ptr<float>(),
-                                 v.data_ptr<float>(), wbf.data_ptr(), (float)lr, lp, cp, (float)b1,
-                                 (float)omb1, (float)b2, (float)omb2, (float)eps,
-                                 (float)weight_decay, cur_stream()),
-            "mt_adam_master");
+  const MtSegments s = master_segments(grads, offsets, master, {m, v}, wbf, "mt_adam_master");
+  const ArenaOptHyper h = adam_hyper(
+      opt_hyper(lr, lr_t, master, weight_decay, 1.0, "mt_adam_master"),
+      corr_ptr(corr, master, "mt_adam_master"), b1, omb1, b2, omb2, eps);
+  update_master(ARENA_OPT_ADAM, s, master, wbf, h, "mt_adam_master");
 }
 
 // LARS: master_segments' checks (mom is the one state buffer) plus trust / slots / workspace /
@@ -771,8 +769,11 @@ void mt_lars_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Ten
                     Tensor mom, Tensor wbf, Tensor trust, std::vector<int64_t> slots,
                     Tensor workspace, double lr, double momentum, double weight_decay, double eeta,
                     double eps, OptT lr_t) {
-  const MtSegments s = master_segments(grads, offsets, master, mom, mom, wbf, "mt_lars_master");
-  const float* lp = opt_lr_ptr(lr_t, master, "mt_lars_master");
+  const MtSegments s = master_segments(grads, offsets, master, {mom}, wbf, "mt_lars_master");
+  ArenaOptHyper h = opt_hyper(lr, lr_t, master, weight_decay, 1.0, "mt_lars_master");
+  h.a = (float)eeta;
+  h.b = (float)momentum;
+  h.eps = (float)eps;
   check_f32(trust, "trust");
   check_f32(workspace, "workspace");
   TORCH_CHECK(trust.device() == master.device() && workspace.device() == master.device(),
@@ -785,45 +786,34 @@ void mt_lars_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Ten
     sl.push_back((int)slots[i]);
   }
   const long long need = arena_mt_lars_workspace_floats(s.ns.data(), (int)s.ns.size());
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(workspace.data_ptr()) % 16 == 0,
-              "mt_lars_master: workspace must be 16-byte aligned");
+  TORCH_CHECK(aligned_to(workspace, 16), "mt_lars_master: workspace must be 16-byte aligned");
   TORCH_CHECK(workspace.numel() >= need, "mt_lars_master: workspace holds ", workspace.numel(),
               " floats, these tensors' blocks need ", need);
-  TORCH_CHECK((float)eeta > 0.f, "mt_lars_master: eeta must be > 0");
-  TORCH_CHECK((float)eps >= 0.f, "mt_lars_master: eps must be >= 0");
+  TORCH_CHECK(h.a > 0.f, "mt_lars_master: eeta must be > 0");
+  TORCH_CHECK(h.eps >= 0.f, "mt_lars_master: eps must be >= 0");
   check_hip(arena_mt_lars_master(s.ptrs.data(), s.offs.data(), s.ns.data(), sl.data(),
-                                 (int)s.ptrs.size(), master.data_ptr<float>(),
-                                 mom.data_ptr<float>(), wbf.data_ptr(), trust.data_ptr<float>(),
-                                 workspace.data_ptr<float>(), (float)lr, lp, (float)momentum,
-                                 (float)weight_decay, (float)eeta, (float)eps, cur_stream()),
+                                 (int)s.ptrs.size(), master.data_ptr<float>(), s.st[0],
+                                 wbf.data_ptr(), trust.data_ptr<float>(),
+                                 workspace.data_ptr<float>(), h, cur_stream()),
             "mt_lars_master");
 }
 
 void mt_rmsprop_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor ms,
                     Tensor mom, double lr, double rho, double omr, double momentum, double eps,
                     double weight_decay, double scale, OptT lr_t) {
-  const MtSegments s = f32_segments(grads, offsets, w, ms, mom, "mt_rmsprop_f32");
-  const float* lp = opt_lr_ptr(lr_t, w, "mt_rmsprop_f32");
-  check_hip(arena_mt_rmsprop_f32(reinterpret_cast<const float* const*>(s.ptrs.data()),
-                                 s.offs.data(), s.ns.data(), (int)s.ptrs.size(),
-                                 w.data_ptr<float>(), ms.data_ptr<float>(), mom.data_ptr<float>(),
-                                 (float)lr, lp, (float)rho, (float)omr, (float)momentum,
-                                 (float)eps, (float)weight_decay, (float)scale, cur_stream()),
-            "mt_rmsprop_f32");
+  const MtSegments s = f32_segments(grads, offsets, w, {ms, mom}, "mt_rmsprop_f32");
+  const ArenaOptHyper h = rmsprop_hyper(
+      opt_hyper(lr, lr_t, w, weight_decay, scale, "mt_rmsprop_f32"), rho, omr, momentum, eps);
+  update_f32(ARENA_OPT_RMSPROP, s, w, h, "mt_rmsprop_f32");
 }
 
 void mt_adam_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor m,
                  Tensor v, Tensor corr, double lr, double b1, double omb1, double b2, double omb2,
                  double eps, double weight_decay, double scale, OptT lr_t) {
-  const MtSegments s = f32_segments(grads, offsets, w, m, v, "mt_adam_f32");
-  const float* lp = opt_lr_ptr(lr_t, w, "mt_adam_f32");
-  const float* cp = corr_ptr(corr, w, "mt_adam_f32");
-  check_hip(arena_mt_adam_f32(reinterpret_cast<const float* const*>(s.ptrs.data()), s.offs.data(),
-                              s.ns.data(), (int)s.ptrs.size(), w.data_ptr<float>(),
-                              m.data_ptr<float>(), v.data_ptr<float>(), (float)lr, lp, cp,
-                              (float)b1, (float)omb1, (float)b2, (float)omb2, (float)eps,
-                              (float)weight_decay, (float)scale, cur_stream()),
-            "mt_adam_f32");
+  const MtSegments s = f32_segments(grads, offsets, w, {m, v}, "mt_adam_f32");
+  const ArenaOptHyper h = adam_hyper(opt_hyper(lr, lr_t, w, weight_decay, scale, "mt_adam_f32"),
+                                     corr_ptr(corr, w, "mt_adam_f32"), b1, omb1, b2, omb2, eps);
+  update_f32(ARENA_OPT_ADAM, s, w, h, "mt_adam_f32");
 }
 
 // The Adam clock's tick: step int64 [1], pow float64 [2] (b1^t, b2^t), corr float32 [1].

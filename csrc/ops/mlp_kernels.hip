@@ -8,9 +8,10 @@
 //   xent_head       logits = H·W2ᵀ + b2 -> loss, accuracy, dlogits, dZ = (dlogits·W2)⊙mask
 //   wgrad_grouped   dW = dZᵀ·X, db = dZᵀ·1 for up to 4 layers in ONE launch, epilogue either
 //                   writes the (scaled) gradient into the flat all-reduce bucket or applies Adam
-//   adam_flat       Adam over the whole flat parameter buffer (after the gradient all-reduce)
 //   softmax_xent    generic row softmax-cross-entropy forward+backward
-//   mt_copy_scale   multi-tensor flatten/unflatten with scale (gradient buckets)
+//
+// Adam over the flat buffer after an all-reduce, the gradient buckets' flatten/unflatten and every
+// other optimizer kernel live in optim_kernels.hip.
 //
 // All matmul work uses the exact-fp32 MFMA v_mfma_f32_16x16x4_f32 (no TF32 on gfx950), so numerics
 // equal an fp32 fmaf chain. Weights are [out][in] (nn.Linear layout), activations row-major.
@@ -1206,42 +1207,6 @@ __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// adam_flat: float4-vectorised Adam over the flat parameter buffer; n must be a multiple of 4.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ P, float* __restrict__ Mm,
-                                                        float* __restrict__ V,
-                                                        const float* __restrict__ G, long long n4,
-                                                        ArenaAdam a, ArenaCounterOp ctr) {
-  counter_op(ctr);
-  const AdamCoef co = adam_coef(a);
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    float4 p = reinterpret_cast<float4*>(P)[i];
-    float4 m = reinterpret_cast<float4*>(Mm)[i];
-    float4 v = reinterpret_cast<float4*>(V)[i];
-    const float4 g = reinterpret_cast<const float4*>(G)[i];
-    adam_apply(co, g.x, p.x, m.x, v.x);
-    adam_apply(co, g.y, p.y, m.y, v.y);
-    adam_apply(co, g.z, p.z, m.z, v.z);
-    adam_apply(co, g.w, p.w, m.w, v.w);
-    reinterpret_cast<float4*>(P)[i] = p;
-    reinterpret_cast<float4*>(Mm)[i] = m;
-    reinterpret_cast<float4*>(V)[i] = v;
-  }
-}
-
-__global__ __launch_bounds__(256) void sgd_flat_kernel(float* __restrict__ P,
-                                                       const float* __restrict__ G, long long n4,
-                                                       float lr, const float* lr_ptr, float gscale) {
-  const float l = lr_ptr ? *lr_ptr : lr;
-  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    float4 p = reinterpret_cast<float4*>(P)[i];
-    const float4 g = reinterpret_cast<const float4*>(G)[i];
-    p.x -= l * g.x * gscale; p.y -= l * g.y * gscale; p.z -= l * g.z * gscale; p.w -= l * g.w * gscale;
-    reinterpret_cast<float4*>(P)[i] = p;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // softmax_xent: generic rows (any C), one wave per row; writes per-row loss and dlogits.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits,
@@ -1267,540 +1232,6 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     for (int cc = lane; cc < C; cc += 64)
       d[cc] = (hw_exp2((x[cc] - lse) * kLog2e) - (cc == y ? 1.f : 0.f)) * grad_scale;
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-// mt_copy_scale: multi-tensor gather/scatter between a list of tensors and one flat bucket.
-//   dir 0: flat[off_i + j] = src_i[j] * scale      (flatten gradients into the all-reduce bucket)
-//   dir 1: dst_i[j] = flat[off_i + j] * scale      (unflatten reduced gradients)
-// ---------------------------------------------------------------------------------------------
-constexpr int kMtMax = 48;
-struct MtArgs {
-  float* ptr[kMtMax];
-  long long off[kMtMax];
-  long long n[kMtMax];
-  int blk_begin[kMtMax + 1];
-  int count;
-};
-
-__global__ __launch_bounds__(256) void mt_copy_scale_kernel(MtArgs a, float* __restrict__ flat,
-                                                            float scale, int dir) {
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const long long base = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024;
-  float* t = a.ptr[ti];
-  float* f = flat + a.off[ti];
-  for (int k = 0; k < 4; ++k) {
-    const long long j = base + k * 256 + threadIdx.x;
-    if (j < a.n[ti]) {
-      if (dir == 0) f[j] = t[j] * scale;
-      else t[j] = f[j] * scale;
-    }
-  }
-}
-
-
-// Momentum SGD over bf16 weights with fp32 master copies (mixed-precision CNN training).
-// Tensor i: bf16 gradient at a.ptr[i] (autograd-owned, same storage order as the parameter),
-// master/momentum/bf16-param segments at a.off[i] of the flat buffers. One pass reads the bf16
-// grad + fp32 master + fp32 momentum and writes master, momentum and the rounded bf16 weight
-// the next forward consumes, so autocast needs no per-step weight/grad casts.
-// Matches torch.optim.SGD (dampening 0, no nesterov): d = g + wd*w; m = mu*m + d; w -= lr*m.
-__device__ inline float bf16_to_f32(uint32_t v) { return __uint_as_float(v << 16); }
-__device__ inline uint32_t f32_to_bf16(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // quiet NaN
-  u += 0x7fffu + ((u >> 16) & 1u);                                  // round to nearest even
-  return u >> 16;
-}
-
-__global__ __launch_bounds__(256) void mt_sgd_master_kernel(MtArgs a, float* __restrict__ master,
-                                                            float* __restrict__ mom,
-                                                            uint16_t* __restrict__ wbf, float lr,
-                                                            const float* lr_ptr, float mu,
-                                                            float wd) {
-  if (lr_ptr) lr = *lr_ptr;  // device learning rate (schedules under graph replay)
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
-  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
-  const long long o = a.off[ti] + j;
-  const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j);
-  float4 w4 = *reinterpret_cast<const float4*>(master + o);
-  float4 m4 = *reinterpret_cast<const float4*>(mom + o);
-  const float g[4] = {bf16_to_f32(g2.x & 0xffffu), bf16_to_f32(g2.x >> 16),
-                      bf16_to_f32(g2.y & 0xffffu), bf16_to_f32(g2.y >> 16)};
-  float* w = &w4.x;
-  float* m = &m4.x;
-  uint32_t r[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    m[k] = mu * m[k] + (g[k] + wd * w[k]);
-    w[k] = w[k] - lr * m[k];
-    r[k] = f32_to_bf16(w[k]);
-  }
-  *reinterpret_cast<float4*>(master + o) = w4;
-  *reinterpret_cast<float4*>(mom + o) = m4;
-  *reinterpret_cast<uint2*>(wbf + o) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
-}
-
-// Momentum SGD over ONE flat range: a data-parallel rank's shard of a gradient bucket after the
-// RCCL reduce-scatter (ShardedMasterSGD's off-node backend). Same arithmetic, in the same order,
-// as the xGMI kernels' shard update (csrc/ccl/xgmi_ccl.hip xgmi_sgd_*): d = g * scale + wd * w,
-// m = mu * m + d, w = w - lr * m. BF16: bf16 summed gradient, fp32 master, rounded bf16 weight
-// written to wbf; else fp32 gradient and the fp32 weights are their own masters. n % 4 == 0 and
-// 16-byte aligned fp32 pointers (host-checked): one thread owns 4 elements per grid-stride step.
-template <bool BF16>
-__global__ __launch_bounds__(256) void shard_sgd_kernel(const void* __restrict__ grad,
-                                                        float* __restrict__ w32,
-                                                        float* __restrict__ mom,
-                                                        uint16_t* __restrict__ wbf, long long n,
-                                                        float lr, const float* lr_ptr, float mu,
-                                                        float wd, float scale) {
-  if (lr_ptr) lr = *lr_ptr;
-  const long long stride = (long long)gridDim.x * 1024;
-  for (long long j = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; j < n; j += stride) {
-    float g[4];
-    if constexpr (BF16) {
-      const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(grad) + j);
-      g[0] = bf16_to_f32(g2.x & 0xffffu);
-      g[1] = bf16_to_f32(g2.x >> 16);
-      g[2] = bf16_to_f32(g2.y & 0xffffu);
-      g[3] = bf16_to_f32(g2.y >> 16);
-    } else {
-      const float4 g4 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(grad) + j);
-      g[0] = g4.x;
-      g[1] = g4.y;
-      g[2] = g4.z;
-      g[3] = g4.w;
-    }
-    float4 w4 = *reinterpret_cast<const float4*>(w32 + j);
-    float4 m4 = *reinterpret_cast<const float4*>(mom + j);
-    float* w = &w4.x;
-    float* m = &m4.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float d = g[k] * scale + wd * w[k];
-      m[k] = mu * m[k] + d;
-      w[k] = w[k] - lr * m[k];
-    }
-    *reinterpret_cast<float4*>(w32 + j) = w4;
-    *reinterpret_cast<float4*>(mom + j) = m4;
-    if constexpr (BF16) {
-      *reinterpret_cast<uint2*>(wbf + j) = make_uint2(f32_to_bf16(w[0]) | (f32_to_bf16(w[1]) << 16),
-                                                      f32_to_bf16(w[2]) | (f32_to_bf16(w[3]) << 16));
-    }
-  }
-}
-
-// Momentum SGD over fp32 tensors with fp32 gradients (BatchNorm scales/shifts, biases), same
-// MtArgs walk as mt_sgd_master: gradient at a.ptr[i], weight/momentum segment at a.off[i] of the
-// flat buffers. Any n and any offset: a thread's 4 elements go through 16-byte accesses when all
-// four exist and the segment and the gradient are 16-byte aligned, else one by one. Arithmetic in
-// shard_sgd_kernel<false>'s order: d = g * scale + wd * w; m = mu * m + d; w -= lr * m.
-__device__ __forceinline__ void sgd32_1(float g, float& w, float& m, float lr, float mu, float wd,
-                                        float scale) {
-  const float d = g * scale + wd * w;
-  m = mu * m + d;
-  w = w - lr * m;
-}
-
-__global__ __launch_bounds__(256) void mt_sgd_f32_kernel(MtArgs a, float* __restrict__ wflat,
-                                                         float* __restrict__ mflat, float lr,
-                                                         const float* lr_ptr, float mu, float wd,
-                                                         float scale) {
-  if (lr_ptr) lr = *lr_ptr;
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const long long n = a.n[ti];
-  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
-  if (j >= n) return;
-  const float* g = a.ptr[ti] + j;
-  float* w = wflat + a.off[ti] + j;
-  float* m = mflat + a.off[ti] + j;
-  // wflat / mflat are 16-byte aligned (host-checked), so the segment is when its offset is
-  const bool vec = j + 4 <= n && (a.off[ti] & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.ptr[ti]) & 15) == 0;
-  if (vec) {
-    const float4 g4 = *reinterpret_cast<const float4*>(g);
-    float4 w4 = *reinterpret_cast<const float4*>(w);
-    float4 m4 = *reinterpret_cast<const float4*>(m);
-    sgd32_1(g4.x, w4.x, m4.x, lr, mu, wd, scale);
-    sgd32_1(g4.y, w4.y, m4.y, lr, mu, wd, scale);
-    sgd32_1(g4.z, w4.z, m4.z, lr, mu, wd, scale);
-    sgd32_1(g4.w, w4.w, m4.w, lr, mu, wd, scale);
-    *reinterpret_cast<float4*>(w) = w4;
-    *reinterpret_cast<float4*>(m) = m4;
-  } else {
-    for (int k = 0; k < 4 && j + k < n; ++k) {
-      float wk = w[k], mk = m[k];
-      sgd32_1(g[k], wk, mk, lr, mu, wd, scale);
-      w[k] = wk;
-      m[k] = mk;
-    }
-  }
-}
-
-// The learning-rate schedule of arena_amd/ops/schedule.py, advanced on the device so a captured
-// step changes its lr from replay to replay. One lane: finds the segment of *step by a linear
-// search over the (at most 64) segments, evaluates it in fp64 exactly as reference_lr does (every
-// operation rounded on its own: no contraction), rounds once to fp32, then counts the step.
-__global__ void lr_schedule_kernel(const long long* __restrict__ seg, int n_seg,
-                                   long long* __restrict__ step, float* __restrict__ lr) {
-  // This unit is built with -ffp-contract=fast, under which the backend fuses a multiply into a
-  // following add whatever `#pragma clang fp contract(off)` or __dmul_rn / __dadd_rn (a plain
-  // `*` / `+` in HIP's headers) say. The empty asm below makes the product an opaque value, so
-  // it is rounded on its own.
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const long long t = *step;
-  int k = 0;
-  for (int i = 1; i < n_seg; ++i)
-    if (t >= seg[4 * i]) k = i;
-  const long long b = seg[4 * k], e = seg[4 * k + 1];
-  const double lr0 = __longlong_as_double(seg[4 * k + 2]);
-  const double lr1 = __longlong_as_double(seg[4 * k + 3]);
-  double v = lr1;                        // the open-ended last segment holds its lr1
-  if (k < n_seg - 1) {
-    v = lr0;
-    if (lr1 != lr0) {
-      const double frac = (double)(t - b) / (double)(e - b);
-      double rise = (lr1 - lr0) * frac;
-      asm volatile("" : "+v"(rise));
-      v = lr0 + rise;
-    }
-  }
-  *lr = (float)v;
-  *step = t + 1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// RMSProp and Adam in TF1's forms (arena_amd/ops/reference.py defines them) over the same MtArgs
-// walk and access pattern as the SGD kernels above. Both start from the coupled gradient
-// d = g * scale + wd * w (scale is 1 on the master path) and keep two fp32 state buffers:
-//   RMSProp (s0 = ms, s1 = mom):  ms = rho * ms + omr * (d * d)
-//                                 mom = mu * mom + lr * d / sqrt(ms + eps);  w = w - mom
-//   Adam    (s0 = m,  s1 = v):    m = b1 * m + omb1 * d;  v = b2 * v + omb2 * (d * d)
-//                                 w = w - (lr * corr) * m / (sqrt(v) + eps)
-// omr / omb1 / omb2 are 1 - rho / 1 - b1 / 1 - b2 formed by the host in fp64: the fp32 difference
-// 1 - float(0.999) is 4.7e-5 off. corr is the bias correction arena_adam_tick keeps on the device.
-// ---------------------------------------------------------------------------------------------
-struct OptHyper {
-  float lr;             // replaced by *lr_ptr when that is set
-  const float* lr_ptr;  // device learning rate (DeviceLR), or null
-  const float* corr;    // Adam: the clock's sqrt(1 - b2^t) / (1 - b1^t); RMSProp: null
-  float a, oma;         // RMSProp: rho, 1 - rho;  Adam: b1, 1 - b1
-  float b, omb;         // RMSProp: mu, unused;    Adam: b2, 1 - b2
-  float eps, wd, scale;
-};
-
-// The per-launch step size: lr for RMSProp, lr * corr for Adam.
-template <bool ADAM>
-__device__ __forceinline__ float opt_step_size(const OptHyper& h) {
-  const float lr = h.lr_ptr ? *h.lr_ptr : h.lr;
-  if constexpr (ADAM) return lr * *h.corr;
-  return lr;
-}
-
-template <bool ADAM>
-__device__ __forceinline__ void opt_1(float g, float& w, float& s0, float& s1, float step,
-                                      const OptHyper& h) {
-  const float d = g * h.scale + h.wd * w;
-  if constexpr (ADAM) {
-    s0 = h.a * s0 + h.oma * d;
-    s1 = h.b * s1 + h.omb * (d * d);
-    w = w - step * s0 / (sqrtf(s1) + h.eps);
-  } else {
-    s0 = h.a * s0 + h.oma * (d * d);
-    s1 = h.b * s1 + step * d / sqrtf(s0 + h.eps);
-    w = w - s1;
-  }
-}
-
-// bf16 gradients, fp32 masters, rounded bf16 weight to wbf: mt_sgd_master_kernel's layout with a
-// second state buffer (28 bytes per element against 22). n % 4 == 0 and offsets % 4 == 0.
-template <bool ADAM>
-__global__ __launch_bounds__(256) void mt_opt_master_kernel(MtArgs a, float* __restrict__ master,
-                                                            float* __restrict__ st0,
-                                                            float* __restrict__ st1,
-                                                            uint16_t* __restrict__ wbf,
-                                                            OptHyper h) {
-  const float step = opt_step_size<ADAM>(h);
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
-  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
-  const long long o = a.off[ti] + j;
-  const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j);
-  float4 w4 = *reinterpret_cast<const float4*>(master + o);
-  float4 p4 = *reinterpret_cast<const float4*>(st0 + o);
-  float4 q4 = *reinterpret_cast<const float4*>(st1 + o);
-  const float g[4] = {bf16_to_f32(g2.x & 0xffffu), bf16_to_f32(g2.x >> 16),
-                      bf16_to_f32(g2.y & 0xffffu), bf16_to_f32(g2.y >> 16)};
-  float* w = &w4.x;
-  float* p = &p4.x;
-  float* q = &q4.x;
-  uint32_t r[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    opt_1<ADAM>(g[k], w[k], p[k], q[k], step, h);
-    r[k] = f32_to_bf16(w[k]);
-  }
-  *reinterpret_cast<float4*>(master + o) = w4;
-  *reinterpret_cast<float4*>(st0 + o) = p4;
-  *reinterpret_cast<float4*>(st1 + o) = q4;
-  *reinterpret_cast<uint2*>(wbf + o) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
-}
-
-// fp32 parameters with fp32 gradients (the BN / bias group): mt_sgd_f32_kernel's walk, any n and
-// any offset, 16-byte accesses under the same alignment test, else one element at a time.
-template <bool ADAM>
-__global__ __launch_bounds__(256) void mt_opt_f32_kernel(MtArgs a, float* __restrict__ wflat,
-                                                         float* __restrict__ st0,
-                                                         float* __restrict__ st1, OptHyper h) {
-  const float step = opt_step_size<ADAM>(h);
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const long long n = a.n[ti];
-  const long long j = (long long)(blockIdx.x - a.blk_begin[ti]) * 1024 + threadIdx.x * 4;
-  if (j >= n) return;
-  const float* g = a.ptr[ti] + j;
-  float* w = wflat + a.off[ti] + j;
-  float* p = st0 + a.off[ti] + j;
-  float* q = st1 + a.off[ti] + j;
-  // the flat buffers are 16-byte aligned (host-checked), so the segment is when its offset is
-  const bool vec = j + 4 <= n && (a.off[ti] & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(a.ptr[ti]) & 15) == 0;
-  if (vec) {
-    const float4 g4 = *reinterpret_cast<const float4*>(g);
-    float4 w4 = *reinterpret_cast<const float4*>(w);
-    float4 p4 = *reinterpret_cast<const float4*>(p);
-    float4 q4 = *reinterpret_cast<const float4*>(q);
-    opt_1<ADAM>(g4.x, w4.x, p4.x, q4.x, step, h);
-    opt_1<ADAM>(g4.y, w4.y, p4.y, q4.y, step, h);
-    opt_1<ADAM>(g4.z, w4.z, p4.z, q4.z, step, h);
-    opt_1<ADAM>(g4.w, w4.w, p4.w, q4.w, step, h);
-    *reinterpret_cast<float4*>(w) = w4;
-    *reinterpret_cast<float4*>(p) = p4;
-    *reinterpret_cast<float4*>(q) = q4;
-  } else {
-    for (int k = 0; k < 4 && j + k < n; ++k) {
-      float wk = w[k], pk = p[k], qk = q[k];
-      opt_1<ADAM>(g[k], wk, pk, qk, step, h);
-      w[k] = wk;
-      p[k] = pk;
-      q[k] = qk;
-    }
-  }
-}
-
-// Adam's clock (arena_amd/ops/optim.py AdamClock), advanced on the device so a captured step
-// keeps correcting the bias from replay to replay. One lane: pw[0] = b1^t and pw[1] = b2^t as
-// running fp64 products, corr = float(sqrt(1 - b2^t) / (1 - b1^t)) with every fp64 operation
-// rounded on its own, exactly as reference_adam_corr does in Python floats. As in
-// lr_schedule_kernel, the empty asm keeps -ffp-contract=fast from fusing each product into the
-// subtraction that follows it.
-__global__ void adam_tick_kernel(long long* __restrict__ step, double* __restrict__ pw,
-                                 float* __restrict__ corr, double b1, double b2) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  double p1 = pw[0] * b1;
-  double p2 = pw[1] * b2;
-  asm volatile("" : "+v"(p1));
-  asm volatile("" : "+v"(p2));
-  pw[0] = p1;
-  pw[1] = p2;
-  *corr = (float)(sqrt(1.0 - p2) / (1.0 - p1));
-  *step = *step + 1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// LARS (arena_amd/ops/reference.py defines it): momentum SGD over bf16 gradients with fp32
-// masters whose step is lr * trust, trust = eeta * |w| / (|g| + wd * |w| + eps) per tensor. Two
-// launches per group of 48 tensors over mt_sgd_master_kernel's walk (1024 elements per block):
-//   mt_lars_norms_kernel   one wave per chunk writes part[chunk] = (sum w^2, sum g^2): 16 serial
-//                          fp32 terms per lane, then the wave64 xor tree.
-//   mt_lars_update_kernel  every block sums ITS tensor's partials in fp64 (lane t takes partials
-//                          t, t + 256, ... in order, then the same tree), forms trust and applies
-//                          mt_sgd_master_kernel's update with step in place of lr.
-// No atomics and nothing to zero: every partial is overwritten at every step. All blocks of a
-// tensor run the same sums over the same values in the same order, so they hold the same trust
-// bit for bit; the tensor's first block stores it to trust[slot].
-// ---------------------------------------------------------------------------------------------
-struct LarsSlots {
-  int slot[kMtMax];  // trust[slot[i]] receives tensor i's trust ratio
-  int part_base;     // this launch group's first (w^2, g^2) pair in the workspace
-};
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void mt_lars_norms_kernel(MtArgs a, LarsSlots s,
-                                                            const float* __restrict__ master,
-                                                            float2* __restrict__ part) {
-  // one wave per 1024-element chunk (the update kernel's block): no LDS, no barrier
-  const int chunk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-  if (chunk >= a.blk_begin[a.count]) return;
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if (chunk >= a.blk_begin[i]) ti = i;
-  const long long n = a.n[ti];
-  const long long j0 = (long long)(chunk - a.blk_begin[ti]) * 1024 + (threadIdx.x & 63) * 4;
-  const uint16_t* gp = reinterpret_cast<const uint16_t*>(a.ptr[ti]);
-  const float* wp = master + a.off[ti];
-  uint2 g2[4];
-  float4 w4[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {  // n % 4 == 0 (host-checked): 4 whole elements or none
-    const long long j = j0 + k * 256;
-    const bool live = j < n;
-    g2[k] = live ? *reinterpret_cast<const uint2*>(gp + j) : make_uint2(0u, 0u);
-    w4[k] = live ? *reinterpret_cast<const float4*>(wp + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  float sw = 0.f, sg = 0.f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float g[4] = {bf16_to_f32(g2[k].x & 0xffffu), bf16_to_f32(g2[k].x >> 16),
-                        bf16_to_f32(g2[k].y & 0xffffu), bf16_to_f32(g2[k].y >> 16)};
-    const float* w = &w4[k].x;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      sw += w[e] * w[e];
-      sg += g[e] * g[e];
-    }
-  }
-  sw = wave_sum(sw);
-  sg = wave_sum(sg);
-  if ((threadIdx.x & 63) == 0) part[s.part_base + chunk] = make_float2(sw, sg);
-}
-
-__global__ __launch_bounds__(256) void mt_lars_update_kernel(
-    MtArgs a, LarsSlots s, float* __restrict__ master, float* __restrict__ mom,
-    uint16_t* __restrict__ wbf, const float2* __restrict__ part, float* __restrict__ trust_out,
-    float lr, const float* lr_ptr, float mu, float wd, float eeta, float eps) {
-  __shared__ double red[8];
-  if (lr_ptr) lr = *lr_ptr;  // device learning rate (schedules under graph replay)
-  int ti = 0;
-  for (int i = 1; i < a.count; ++i)
-    if ((int)blockIdx.x >= a.blk_begin[i]) ti = i;
-  const int first = a.blk_begin[ti];
-  const int nb = a.blk_begin[ti + 1] - first;
-  const float2* p = part + s.part_base + first;
-  double sw = 0.0, sg = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 1024) {  // 4 loads in flight, summed in index order
-    float2 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      v[k] = i + k * 256 < nb ? p[i + k * 256] : make_float2(0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sw += (double)v[k].x;
-      sg += (double)v[k].y;
-    }
-  }
-  sw = wave_sum_f64(sw);
-  sg = wave_sum_f64(sg);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = sw;
-    red[4 + (threadIdx.x >> 6)] = sg;
-  }
-  __syncthreads();
-  const float wn = (float)sqrt(((red[0] + red[1]) + red[2]) + red[3]);
-  const float gn = (float)sqrt(((red[4] + red[5]) + red[6]) + red[7]);
-  float trust = 1.f;
-  if (wn > 0.f && gn > 0.f) {
-    // fp32 operations in the reference's order; as in lr_schedule_kernel, the empty asm keeps
-    // -ffp-contract=fast from fusing a product into the sum that follows it
-    float num = eeta * wn;
-    float dec = wd * wn;
-    asm volatile("" : "+v"(num));
-    asm volatile("" : "+v"(dec));
-    trust = num / ((gn + dec) + eps);
-  }
-  float step = lr * trust;
-  asm volatile("" : "+v"(step));
-  if ((int)blockIdx.x == first && threadIdx.x == 0) trust_out[s.slot[ti]] = trust;
-  const long long j = (long long)(blockIdx.x - first) * 1024 + threadIdx.x * 4;
-  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
-  const long long o = a.off[ti] + j;
-  const uint2 g2 = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j);
-  float4 w4 = *reinterpret_cast<const float4*>(master + o);
-  float4 m4 = *reinterpret_cast<const float4*>(mom + o);
-  const float g[4] = {bf16_to_f32(g2.x & 0xffffu), bf16_to_f32(g2.x >> 16),
-                      bf16_to_f32(g2.y & 0xffffu), bf16_to_f32(g2.y >> 16)};
-  float* w = &w4.x;
-  float* m = &m4.x;
-  uint32_t r[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    m[k] = mu * m[k] + (g[k] + wd * w[k]);
-    w[k] = w[k] - step * m[k];
-    r[k] = f32_to_bf16(w[k]);
-  }
-  *reinterpret_cast<float4*>(master + o) = w4;
-  *reinterpret_cast<float4*>(mom + o) = m4;
-  *reinterpret_cast<uint2*>(wbf + o) = make_uint2(r[0] | (r[1] << 16), r[2] | (r[3] << 16));
-}
-
-// Fills MtArgs for tensors [base, base + cnt) and returns the launch's block count.
-inline int mt_fill(MtArgs& a, const void* const* ptrs, const long long* offs, const long long* ns,
-                   int base, int cnt) {
-  int blocks = 0;
-  for (int i = 0; i < cnt; ++i) {
-    a.ptr[i] = const_cast<float*>(reinterpret_cast<const float*>(ptrs[base + i]));
-    a.off[i] = offs[base + i];
-    a.n[i] = ns[base + i];
-    a.blk_begin[i] = blocks;
-    blocks += (int)((ns[base + i] + 1023) / 1024);
-  }
-  a.blk_begin[cnt] = blocks;
-  a.count = cnt;
-  return blocks;
-}
-
-template <bool ADAM>
-hipError_t launch_opt_master(const void* const* grads, const long long* offs, const long long* ns,
-                             int count, float* master, float* st0, float* st1, void* wbf,
-                             const OptHyper& h, hipStream_t stream) {
-  if (ADAM && !h.corr) return hipErrorInvalidValue;
-  for (int i = 0; i < count; ++i)
-    if (ns[i] < 0 || offs[i] < 0 || ns[i] % 4 || offs[i] % 4) return hipErrorInvalidValue;
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    const int blocks = mt_fill(a, grads, offs, ns, base, std::min(kMtMax, count - base));
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(mt_opt_master_kernel<ADAM>, dim3(blocks), dim3(256), 0, stream, a, master,
-                       st0, st1, reinterpret_cast<uint16_t*>(wbf), h);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <bool ADAM>
-hipError_t launch_opt_f32(const float* const* grads, const long long* offs, const long long* ns,
-                          int count, float* w, float* st0, float* st1, const OptHyper& h,
-                          hipStream_t stream) {
-  if (ADAM && !h.corr) return hipErrorInvalidValue;
-  for (int i = 0; i < count; ++i)
-    if (ns[i] < 0 || offs[i] < 0) return hipErrorInvalidValue;
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    const int blocks = mt_fill(a, reinterpret_cast<const void* const*>(grads), offs, ns, base,
-                               std::min(kMtMax, count - base));
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(mt_opt_f32_kernel<ADAM>, dim3(blocks), dim3(256), 0, stream, a, w, st0, st1,
-                       h);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
 }
 
 }  // namespace
@@ -2005,216 +1436,10 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
   return hipGetLastError();
 }
 
-hipError_t arena_adam_flat(float* P, float* M, float* V, const float* G, long long n,
-                           ArenaAdam adam, ArenaCounterOp ctr, hipStream_t stream) {
-  if (n % 4) return hipErrorInvalidValue;
-  const long long n4 = n / 4;
-  const int blocks = (int)std::min<long long>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, P, M, V,
-                     G, n4, adam, ctr);
-  return hipGetLastError();
-}
-
-hipError_t arena_sgd_flat(float* P, const float* G, long long n, float lr, const float* lr_ptr,
-                          float gscale, hipStream_t stream) {
-  if (n % 4) return hipErrorInvalidValue;
-  const long long n4 = n / 4;
-  const int blocks = (int)std::min<long long>((n4 + 255) / 256, 2048);
-  hipLaunchKernelGGL(sgd_flat_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, stream, P, G, n4,
-                     lr, lr_ptr, gscale);
-  return hipGetLastError();
-}
-
 hipError_t arena_softmax_xent(const float* logits, const long long* labels, int M, int C,
                               float* loss, float* dlogits, float grad_scale, hipStream_t stream) {
   hipLaunchKernelGGL(softmax_xent_kernel, dim3((M + 3) / 4), dim3(256), 0, stream, logits, labels,
                      M, C, loss, dlogits, grad_scale);
-  return hipGetLastError();
-}
-
-// ptrs/offs/ns arrays of length count (any count; chunked into launches of kMtMax tensors).
-hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const long long* ns,
-                               int count, float* flat, float scale, int dir, hipStream_t stream) {
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    const int cnt = std::min(kMtMax, count - base);
-    int blocks = 0;
-    for (int i = 0; i < cnt; ++i) {
-      a.ptr[i] = ptrs[base + i];
-      a.off[i] = offs[base + i];
-      a.n[i] = ns[base + i];
-      a.blk_begin[i] = blocks;
-      blocks += (int)((ns[base + i] + 1023) / 1024);
-    }
-    a.blk_begin[cnt] = blocks;
-    a.count = cnt;
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(mt_copy_scale_kernel, dim3(blocks), dim3(256), 0, stream, a, flat, scale,
-                       dir);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// grads[i]: bf16 gradient pointers; offs/ns: segment offsets (multiples of 4) and sizes (n % 4 == 0).
-hipError_t arena_mt_sgd_master(const void* const* grads, const long long* offs, const long long* ns,
-                               int count, float* master, float* mom, void* wbf, float lr,
-                               const float* lr_ptr, float mu, float wd, hipStream_t stream) {
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    const int cnt = std::min(kMtMax, count - base);
-    int blocks = 0;
-    for (int i = 0; i < cnt; ++i) {
-      if (ns[base + i] % 4 || offs[base + i] % 4) return hipErrorInvalidValue;
-      a.ptr[i] = const_cast<float*>(reinterpret_cast<const float*>(grads[base + i]));
-      a.off[i] = offs[base + i];
-      a.n[i] = ns[base + i];
-      a.blk_begin[i] = blocks;
-      blocks += (int)((ns[base + i] + 1023) / 1024);
-    }
-    a.blk_begin[cnt] = blocks;
-    a.count = cnt;
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(mt_sgd_master_kernel, dim3(blocks), dim3(256), 0, stream, a, master, mom,
-                       reinterpret_cast<uint16_t*>(wbf), lr, lr_ptr, mu, wd);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
-                           long long n, float lr, const float* lr_ptr, float mu, float wd,
-                           float scale, hipStream_t stream) {
-  if (n % 4 || (grad_bf16 && !wbf)) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  const long long blocks = std::min<long long>((n + 1023) / 1024, 4096);
-  if (grad_bf16)
-    hipLaunchKernelGGL(shard_sgd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, stream, grad,
-                       w32, mom, reinterpret_cast<uint16_t*>(wbf), n, lr, lr_ptr, mu, wd, scale);
-  else
-    hipLaunchKernelGGL(shard_sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, grad,
-                       w32, mom, nullptr, n, lr, lr_ptr, mu, wd, scale);
-  return hipGetLastError();
-}
-
-// grads[i]: fp32 gradient pointers; offs/ns: segment offsets and sizes in w / mom (any values).
-hipError_t arena_mt_sgd_f32(const float* const* grads, const long long* offs, const long long* ns,
-                            int count, float* w, float* mom, float lr, const float* lr_ptr,
-                            float mu, float wd, float scale, hipStream_t stream) {
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    const int cnt = std::min(kMtMax, count - base);
-    int blocks = 0;
-    for (int i = 0; i < cnt; ++i) {
-      if (ns[base + i] < 0 || offs[base + i] < 0) return hipErrorInvalidValue;
-      a.ptr[i] = const_cast<float*>(grads[base + i]);
-      a.off[i] = offs[base + i];
-      a.n[i] = ns[base + i];
-      a.blk_begin[i] = blocks;
-      blocks += (int)((ns[base + i] + 1023) / 1024);
-    }
-    a.blk_begin[cnt] = blocks;
-    a.count = cnt;
-    if (blocks == 0) continue;
-    hipLaunchKernelGGL(mt_sgd_f32_kernel, dim3(blocks), dim3(256), 0, stream, a, w, mom, lr, lr_ptr,
-                       mu, wd, scale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
-                             hipStream_t stream) {
-  if (n_seg < 1 || n_seg > 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, seg, n_seg, step, lr);
-  return hipGetLastError();
-}
-
-// RMSProp / Adam over bf16 gradients with fp32 masters: offs / ns multiples of 4, as
-// arena_mt_sgd_master. omr, omb1, omb2: 1 - rho, 1 - b1, 1 - b2, formed by the caller in fp64.
-hipError_t arena_mt_rmsprop_master(const void* const* grads, const long long* offs,
-                                   const long long* ns, int count, float* master, float* ms,
-                                   float* mom, void* wbf, float lr, const float* lr_ptr, float rho,
-                                   float omr, float mu, float eps, float wd, hipStream_t stream) {
-  const OptHyper h{lr, lr_ptr, nullptr, rho, omr, mu, 0.f, eps, wd, 1.f};
-  return launch_opt_master<false>(grads, offs, ns, count, master, ms, mom, wbf, h, stream);
-}
-
-hipError_t arena_mt_adam_master(const void* const* grads, const long long* offs,
-                                const long long* ns, int count, float* master, float* m, float* v,
-                                void* wbf, float lr, const float* lr_ptr, const float* corr,
-                                float b1, float omb1, float b2, float omb2, float eps, float wd,
-                                hipStream_t stream) {
-  const OptHyper h{lr, lr_ptr, corr, b1, omb1, b2, omb2, eps, wd, 1.f};
-  return launch_opt_master<true>(grads, offs, ns, count, master, m, v, wbf, h, stream);
-}
-
-// The same over fp32 tensors with fp32 gradients (any sizes and offsets), as arena_mt_sgd_f32.
-hipError_t arena_mt_rmsprop_f32(const float* const* grads, const long long* offs,
-                                const long long* ns, int count, float* w, float* ms, float* mom,
-                                float lr, const float* lr_ptr, float rho, float omr, float mu,
-                                float eps, float wd, float scale, hipStream_t stream) {
-  const OptHyper h{lr, lr_ptr, nullptr, rho, omr, mu, 0.f, eps, wd, scale};
-  return launch_opt_f32<false>(grads, offs, ns, count, w, ms, mom, h, stream);
-}
-
-hipError_t arena_mt_adam_f32(const float* const* grads, const long long* offs, const long long* ns,
-                             int count, float* w, float* m, float* v, float lr,
-                             const float* lr_ptr, const float* corr, float b1, float omb1, float b2,
-                             float omb2, float eps, float wd, float scale, hipStream_t stream) {
-  const OptHyper h{lr, lr_ptr, corr, b1, omb1, b2, omb2, eps, wd, scale};
-  return launch_opt_f32<true>(grads, offs, ns, count, w, m, v, h, stream);
-}
-
-long long arena_mt_lars_workspace_floats(const long long* ns, int count) {
-  long long blocks = 0;
-  for (int i = 0; i < count; ++i) blocks += (ns[i] + 1023) / 1024;
-  return 2 * blocks;
-}
-
-// LARS over bf16 gradients with fp32 masters: offs / ns multiples of 4, as arena_mt_sgd_master.
-// slots[i]: tensor i's entry of trust. workspace: arena_mt_lars_workspace_floats(ns, count) floats,
-// 16-byte aligned, contents irrelevant: one (w^2, g^2) pair per 1024-element block, each launch
-// group in its own range.
-hipError_t arena_mt_lars_master(const void* const* grads, const long long* offs,
-                                const long long* ns, const int* slots, int count, float* master,
-                                float* mom, void* wbf, float* trust, float* workspace, float lr,
-                                const float* lr_ptr, float mu, float wd, float eeta, float eps,
-                                hipStream_t stream) {
-  if (!trust || !workspace || !(eeta > 0.f) || !(eps >= 0.f)) return hipErrorInvalidValue;
-  for (int i = 0; i < count; ++i)
-    if (ns[i] < 0 || offs[i] < 0 || ns[i] % 4 || offs[i] % 4 || slots[i] < 0)
-      return hipErrorInvalidValue;
-  float2* part = reinterpret_cast<float2*>(workspace);
-  int part_base = 0;
-  for (int base = 0; base < count; base += kMtMax) {
-    MtArgs a;
-    LarsSlots s;
-    const int cnt = std::min(kMtMax, count - base);
-    const int blocks = mt_fill(a, grads, offs, ns, base, cnt);
-    if (blocks == 0) continue;
-    for (int i = 0; i < kMtMax; ++i) s.slot[i] = i < cnt ? slots[base + i] : 0;
-    s.part_base = part_base;
-    part_base += blocks;
-    hipLaunchKernelGGL(mt_lars_norms_kernel, dim3((blocks + 3) / 4), dim3(256), 0, stream, a, s,
-                       master, part);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mt_lars_update_kernel, dim3(blocks), dim3(256), 0, stream, a, s, master,
-                       mom, reinterpret_cast<uint16_t*>(wbf), part, trust, lr, lr_ptr, mu, wd,
-                       eeta, eps);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-hipError_t arena_adam_tick(long long* step, double* pw, float* corr, double b1, double b2,
-                           hipStream_t stream) {
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, stream, step, pw, corr, b1, b2);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """MasterSGD (bf16 weights + fp32 masters, one multi-tensor kernel) vs torch.optim.SGD in fp32.
 
 CPU: the PyTorch reference path of ``mt_sgd_master``; GPU: the HIP kernel
-(``csrc/ops/mlp_kernels.hip::mt_sgd_master_kernel``)."""
+(``csrc/ops/optim_kernels.hip::mt_master_kernel<SgdRule>``)."""
 import pytest
 import torch
 

@@ -1,5 +1,6 @@
 """RMSProp and Adam on the GPU: the ``arena_adam_tick`` kernel bit for bit against
-``reference_adam_corr``, the four multi-tensor update kernels against their CPU references, a
+``reference_adam_corr``, the multi-tensor update kernels (with momentum SGD, which runs the same
+master-layout kernel under another rule) against their CPU references, a
 captured step whose bias correction (and learning rate) moves from replay to replay, ``TFAdam``
 under capture, and ``cnn_bench --optimizer`` end to end."""
 from __future__ import annotations
@@ -23,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BF16 = torch.bfloat16
 WD = 4e-5
 TOL = dict(rtol=1e-5, atol=1e-6)
-LR = {"rmsprop": 0.01, "adam": 0.001}
+LR = {"rmsprop": 0.01, "adam": 0.001, "sgd": 0.01}
 SENTINEL = 96.0           # exact in bf16 too
 
 
@@ -87,6 +88,8 @@ def _run_master(name, dev, lr_form):
             clock.tick()
             fused.mt_adam_master(grads, offs, master, s0, s1, wbf, clock.corr, weight_decay=WD,
                                  **kw)
+        elif name == "sgd":                           # one state buffer: s1 is passed to nothing
+            fused.mt_sgd_master(grads, offs, master, s0, wbf, momentum=0.9, weight_decay=WD, **kw)
         else:
             fused.mt_rmsprop_master(grads, offs, master, s0, s1, wbf, weight_decay=WD, **kw)
     return master.cpu(), s0.cpu(), s1.cpu(), wbf.cpu()
@@ -103,10 +106,12 @@ def _master_ref(name):
 
 
 @pytest.mark.parametrize("lr_form", ["float", "lr_t", "ignored_float"])
-@pytest.mark.parametrize("name", ["rmsprop", "adam"])
+@pytest.mark.parametrize("name", ["rmsprop", "adam", "sgd"])
 def test_master_kernels_match_cpu_reference(cuda, name, lr_form):
     w, s0, s1, wbf = _run_master(name, cuda, lr_form)
     rw, rs0, rs1, _ = _master_ref(name)
+    if name == "sgd":
+        assert torch.equal(s1, _master_set()[4]) and torch.equal(rs1, s1)   # untouched
     assert not torch.equal(rw, _master_set()[2])          # the reference did move
     torch.testing.assert_close(w, rw, **TOL)
     torch.testing.assert_close(s0, rs0, **TOL)
@@ -190,6 +195,23 @@ def test_bindings_check_their_arguments(cuda):
         fused.mt_adam_master([g], [0], w, a[:8], b, wbf, corr, lr=0.1)
     with pytest.raises(RuntimeError, match="dense bf16"):
         fused.mt_rmsprop_master([g.float()], [0], w, a, b, wbf, lr=0.1)
+    sgd = dict(lr=0.1, momentum=0.9, weight_decay=0.0)
+    with pytest.raises(RuntimeError, match="out of bounds"):
+        fused.mt_sgd_master([g], [4], w, a, wbf, **sgd)
+    with pytest.raises(RuntimeError, match="misaligned"):
+        fused.mt_sgd_master([g[:6]], [0], w, a, wbf, **sgd)
+    with pytest.raises(RuntimeError, match="equal size"):
+        fused.mt_sgd_master([g], [0], w, a[:8], wbf, **sgd)
+    with pytest.raises(RuntimeError, match="dense bf16"):
+        fused.mt_sgd_master([g.float()], [0], w, a, wbf, **sgd)
+    w17 = torch.zeros(n + 1, device=cuda)                 # a master that starts 4 bytes in
+    assert w17[1:].data_ptr() % 16 == 4
+    with pytest.raises(RuntimeError, match="16-byte"):
+        fused.mt_sgd_master([g], [0], w17[1:], a, wbf, **sgd)
+    with pytest.raises(RuntimeError, match="out of bounds"):
+        fused.mt_sgd_f32([w.clone()], [1], w, a, **sgd)
+    with pytest.raises(RuntimeError, match="dense fp32"):
+        fused.mt_sgd_f32([g], [0], w, a, **sgd)
     with pytest.raises(RuntimeError, match="out of bounds"):
         fused.mt_adam_f32([w.clone()], [1], w, a, b, corr, lr=0.1)
     with pytest.raises(RuntimeError, match="dense fp32"):
@@ -202,7 +224,7 @@ def test_bindings_check_their_arguments(cuda):
         fused.adam_tick(torch.zeros(1, dtype=torch.int64, device=cuda),
                         torch.ones(2, dtype=torch.float32, device=cuda), corr, 0.9, 0.999)
     torch.cuda.synchronize()
-    assert not w.any() and not a.any() and not b.any()
+    assert not w.any() and not a.any() and not b.any() and not w17.any() and not wbf.any()
 
 
 # ------------------------------------------------------------------------------- graph replay
