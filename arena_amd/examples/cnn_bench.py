@@ -130,6 +130,13 @@ def parse(argv=None):
                          "multi-tensor HIP kernel; with several ranks by the sharded xGMI "
                          "reduce-scatter/SGD/all-gather kernel (auto: on for bf16 GPU runs, "
                          "data parallel only when the xGMI collective is usable)")
+    ap.add_argument("--shard_optimizer", action="store_true",
+                    help="data parallel with --optimizer rmsprop / adam or --lars (bf16 on GPUs): "
+                         "keep bf16 conv / fc weights with fp32 masters sharded over the ranks and "
+                         "run the rule in fused kernels between an RCCL reduce-scatter and "
+                         "all-gather (--comm auto, rccl or hier), instead of the fp32 "
+                         "DistributedOptimizer path. Opt-in: the two have not been compared on "
+                         "a multi-GPU node")
     ap.add_argument("--async_wgrad", choices=["on", "off"], default="off",
                     help="conv weight gradients on a second HIP stream, concurrent with the "
                          "backward-data/BatchNorm chain (single rank; measured slower on "
@@ -364,24 +371,45 @@ def build(args, dev, world, segments=None):
     mw = getattr(args, "master_weights", "auto")
     name = getattr(args, "optimizer", "momentum")
     momentum = 0.0 if name == "sgd" else args.momentum
-    if name in ("rmsprop", "adam") and world > 1:
-        if mw == "on":
-            raise SystemExit(f"--optimizer {name} --master_weights on: the sharded xGMI / RCCL "
-                             "update of data-parallel master weights (ShardedMasterSGD) implements "
-                             "momentum SGD only; use --master_weights off")
-        mw = "off"
     lars = bool(getattr(args, "lars", False))
-    if lars and world > 1:
+    rule = "lars" if lars else name if name in ("rmsprop", "adam") else "sgd"
+    comm = getattr(args, "comm", "auto")
+    bf16_gpu = dev.type == "cuda" and getattr(args, "dtype", "bf16") == "bf16"
+    # --shard_optimizer: the rule runs inside ShardedMasterSGD over RCCL (opt-in; momentum SGD and
+    # single-rank runs are what they were without it)
+    shard = bool(getattr(args, "shard_optimizer", False)) and world > 1 and rule != "sgd"
+    if shard:
+        if not bf16_gpu:
+            raise SystemExit("--shard_optimizer needs --dtype bf16 on a GPU (the conv / fc weights "
+                             "become bf16 with sharded fp32 masters, updated by HIP kernels)")
+        if comm == "xgmi":
+            raise SystemExit(f"--shard_optimizer --comm xgmi: the xGMI kernels implement momentum "
+                             f"SGD only; {rule} shards over --comm auto, rccl or hier")
+        if mw == "off":
+            raise SystemExit("--shard_optimizer keeps sharded master weights: it excludes "
+                             "--master_weights off")
+        mw = "on"
+    elif name in ("rmsprop", "adam") and world > 1:
         if mw == "on":
-            raise SystemExit("--lars --master_weights on: the sharded xGMI / RCCL update of "
-                             "data-parallel master weights (ShardedMasterSGD) implements momentum "
-                             "SGD only (LARS needs per-tensor norms across shards); use "
+            raise SystemExit(f"--optimizer {name} --master_weights on: the xGMI kernels of the "
+                             "sharded data-parallel update (ShardedMasterSGD) implement "
+                             "momentum SGD only; add --shard_optimizer (RCCL / hier, bf16 on a "
+                             "GPU) or use --master_weights off")
+        mw = "off"
+    elif lars and world > 1:
+        if mw == "on":
+            raise SystemExit("--lars --master_weights on: the xGMI kernels of the sharded "
+                             "data-parallel update (ShardedMasterSGD) implement momentum SGD only; "
+                             "add --shard_optimizer (RCCL / hier, bf16 on a GPU) or use "
                              "--master_weights off")
         mw = "off"
     model = build_model(args, dev)
     decay, no_decay = [], []
     for n, p in model.named_parameters():
         (no_decay if p.ndim <= 1 else decay).append(p)   # no decay on BN / bias
+    if shard and lars and any(p.numel() % 4 for p in decay):
+        raise SystemExit("--shard_optimizer --lars needs every conv / fc weight's element count "
+                         "to be a multiple of 4")
     master = mw == "on" or (
         mw == "auto" and dev.type == "cuda"
         and getattr(args, "dtype", "bf16") == "bf16" and all(p.numel() % 4 == 0 for p in decay))
@@ -399,12 +427,21 @@ def build(args, dev, world, segments=None):
         # where every rank's GPU is mapped into every rank (one node), else over RCCL
         # reduce-scatter / shard update / all-gather (decided collectively: all ranks agree)
         from ..parallel.zero import ShardedMasterSGD
-        comm = getattr(args, "comm", "auto")
+        hyper = {}
+        if shard and rule == "rmsprop":
+            momentum = args.rmsprop_momentum
+            hyper = {"rule": rule, "decay": args.rmsprop_decay, "eps": args.rmsprop_epsilon}
+        elif shard and rule == "adam":
+            hyper = {"rule": rule, "betas": (args.adam_beta1, args.adam_beta2),
+                     "eps": args.adam_epsilon}
+        elif shard:
+            hyper = {"rule": rule, "eeta": getattr(args, "lars_eeta", LARS_FLAGS["lars_eeta"]),
+                     "eps": getattr(args, "lars_epsilon", LARS_FLAGS["lars_epsilon"])}
         opt = ShardedMasterSGD(
             [{"params": decay, "weight_decay": args.weight_decay},
              {"params": no_decay, "weight_decay": 0.0, "weights": "fp32"}],
             lr=lr, momentum=momentum, bucket_mb=args.bucket_mb,
-            backend=comm, order=list(model.parameters()))
+            backend=comm, order=list(model.parameters()), **hyper)
         if hvd.rank() == 0 and opt.backend != "xgmi" and comm == "auto":
             print(f"[rank 0] ShardedMasterSGD over RCCL, {opt.backend} (ranks cannot map each "
                   "other's GPUs)", file=sys.stderr, flush=True)
@@ -502,7 +539,7 @@ def comm_name(opt) -> str:
         red = ""
         if opt.backend in ("rccl", "hier"):
             red = ",fp32-reduce" if opt.rccl_reduce_fp32 else ",bf16-ring-reduce"
-        return f"{opt.backend}-sharded-sgd[{len(opt.buckets)} buckets{red}]"
+        return f"{opt.backend}-sharded-{opt.rule}[{len(opt.buckets)} buckets{red}]"
     c = getattr(opt, "comm", None)
     return c if isinstance(c, str) else "none"
 

@@ -181,7 +181,15 @@ def shard_sgd(grad: Tensor, w32: Tensor, mom: Tensor, wbf: Optional[Tensor] = No
               lr_t: Optional[Tensor] = None) -> None:
     """Momentum SGD over one flat range (a rank's shard of a reduce-scattered bucket):
     d = grad * scale + wd * w32; mom = momentum * mom + d; w32 -= lr * mom; with bf16 ``grad``
-    the fp32 ``w32`` are masters and ``wbf`` receives the rounded bf16 weights."""
+    the fp32 ``w32`` are masters and ``wbf`` receives the rounded bf16 weights. An fp32 ``grad``
+    with ``wbf`` is the wide layout (a reduce-scatter that summed in fp32 over fp32 masters of
+    bf16 weights), which the ``shard_update`` kernel runs."""
+    if w32.is_cuda and wbf is not None and grad.dtype == torch.float32:
+        _ext.load().shard_update(rule=reference.OPT_SGD, grad=grad, w32=w32, st0=mom, wbf=wbf,
+                                 lr=float(lr), a=0.0, oma=0.0, b=float(momentum), omb=0.0, eps=0.0,
+                                 weight_decay=float(weight_decay), scale=float(scale),
+                                 lr_t=_check_lr_t(lr_t, w32))
+        return
     _impl(w32).shard_sgd(grad, w32, mom, wbf, float(lr), float(momentum), float(weight_decay),
                          float(scale), lr_t=_check_lr_t(lr_t, w32))
 
@@ -280,6 +288,66 @@ def mt_lars_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tens
                                  [int(s) for s in slots], workspace, float(lr), float(momentum),
                                  float(weight_decay), float(eeta), float(eps),
                                  lr_t=_check_lr_t(lr_t, master))
+
+
+def shard_rmsprop(grad: Tensor, w32: Tensor, ms: Tensor, mom: Tensor,
+                  wbf: Optional[Tensor] = None, *, lr: float, decay: float = 0.9,
+                  momentum: float = 0.9, eps: float = 1.0, weight_decay: float = 0.0,
+                  scale: float = 1.0, lr_t: Optional[Tensor] = None) -> None:
+    """TF1 RMSProp over one flat range (a rank's shard of a reduce-scattered bucket), d = grad *
+    scale + wd * w32, in :func:`shard_sgd`'s three layouts: bf16 ``grad`` with ``wbf`` (fp32
+    masters, rounded bf16 weights written), fp32 ``grad`` without (the fp32 weights are their own
+    masters), fp32 ``grad`` with ``wbf`` (wide)."""
+    _impl(w32).shard_update(rule=reference.OPT_RMSPROP, grad=grad, w32=w32, st0=ms, st1=mom,
+                            wbf=wbf, lr=float(lr), a=float(decay), oma=_one_minus(decay),
+                            b=float(momentum), omb=0.0, eps=float(eps),
+                            weight_decay=float(weight_decay), scale=float(scale),
+                            lr_t=_check_lr_t(lr_t, w32))
+
+
+def shard_adam(grad: Tensor, w32: Tensor, m: Tensor, v: Tensor, corr: Tensor,
+               wbf: Optional[Tensor] = None, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+               weight_decay: float = 0.0, scale: float = 1.0,
+               lr_t: Optional[Tensor] = None) -> None:
+    """TF1 Adam over one flat range, the layouts of :func:`shard_rmsprop`; ``corr`` (fp32 [1]) is
+    the bias correction of this step, kept on the device by :func:`adam_tick`."""
+    b1, b2 = float(betas[0]), float(betas[1])
+    _impl(w32).shard_update(rule=reference.OPT_ADAM, grad=grad, w32=w32, st0=m, st1=v, wbf=wbf,
+                            corr=_check_corr(corr, w32), lr=float(lr), a=b1, oma=_one_minus(b1),
+                            b=b2, omb=_one_minus(b2), eps=float(eps),
+                            weight_decay=float(weight_decay), scale=float(scale),
+                            lr_t=_check_lr_t(lr_t, w32))
+
+
+def shard_lars_norms(grad: Tensor, master: Tensor, goffs: Sequence[int], moffs: Sequence[int],
+                     ns: Sequence[int], slots: Sequence[int], sums: Tensor, workspace: Tensor, *,
+                     scale: float) -> None:
+    """Sharded LARS, first half. ``grad``: a rank's shard of a summed (bf16 or fp32) gradient;
+    piece i is ``ns[i]`` elements at ``grad[goffs[i]:]`` and ``master[moffs[i]:]`` of tensor
+    ``slots[i]``. ``sums`` (fp64, two entries per tensor of the sub-range) receives the sums of
+    w^2 and (g * scale)^2 over this rank's piece of each tensor, 0.0 without one. The caller
+    all-reduces ``sums`` before :func:`shard_lars_update`. ``workspace``: fp32, at least
+    ``mt_lars_workspace_floats(ns)`` elements. Deterministic: no atomics."""
+    _impl(master).shard_lars_norms(grad, master, [int(o) for o in goffs], [int(o) for o in moffs],
+                                   [int(n) for n in ns], [int(s) for s in slots], sums, workspace,
+                                   float(scale))
+
+
+def shard_lars_update(grad: Tensor, master: Tensor, mom: Tensor, wbf: Tensor,
+                      goffs: Sequence[int], moffs: Sequence[int], ns: Sequence[int],
+                      slots: Sequence[int], sums: Tensor, trust: Tensor, *, lr: float,
+                      momentum: float, weight_decay: float = 0.0, eeta: float = 0.001,
+                      eps: float = 0.0, scale: float = 1.0,
+                      lr_t: Optional[Tensor] = None) -> None:
+    """Sharded LARS, second half: ``trust[s]`` for every tensor of the sub-range from the reduced
+    ``sums`` (1.0 when a norm is 0), then d = g * scale + wd * w; m = momentum * m + d; w -= (lr *
+    trust) * m over this rank's pieces, rounded bf16 weights to ``wbf``. ``master`` / ``mom`` /
+    ``wbf``: the flat buffers ``moffs`` index."""
+    _impl(master).shard_lars_update(grad, master, mom, wbf, [int(o) for o in goffs],
+                                    [int(o) for o in moffs], [int(n) for n in ns],
+                                    [int(s) for s in slots], sums, trust, float(lr),
+                                    float(momentum), float(weight_decay), float(eeta), float(eps),
+                                    float(scale), lr_t=_check_lr_t(lr_t, master))
 
 
 def adam_tick(step: Tensor, pow: Tensor, corr: Tensor, b1: float, b2: float) -> None:

@@ -447,8 +447,13 @@ def _sum_squares(v: torch.Tensor) -> float:
 
 def reference_lars_trust(w, g, eeta, weight_decay, eps) -> torch.Tensor:
     """LARS's trust ratio of one tensor (flat fp32 ``w`` and ``g``) as an fp32 scalar tensor."""
-    wn = _f32(math.sqrt(_sum_squares(w)))
-    gn = _f32(math.sqrt(_sum_squares(g)))
+    return lars_trust_of_sums(_sum_squares(w), _sum_squares(g), eeta, weight_decay, eps)
+
+
+def lars_trust_of_sums(sw: float, sg: float, eeta, weight_decay, eps) -> torch.Tensor:
+    """The trust ratio from the two fp64 sums of squares (sharded LARS all-reduces them)."""
+    wn = _f32(math.sqrt(float(sw)))
+    gn = _f32(math.sqrt(float(sg)))
     if not (wn > 0 and gn > 0):
         return _f32(1.0)
     return _f32(eeta) * wn / (gn + _f32(weight_decay) * wn + _f32(eps))
@@ -489,6 +494,69 @@ def shard_sgd(grad, w32, mom, wbf, lr, momentum, weight_decay, scale, lr_t=None)
     w32.sub_(lr * mom)
     if wbf is not None:
         wbf.copy_(w32)
+
+
+OPT_SGD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2      # csrc/ops/abi.h ARENA_OPT_*
+
+
+def shard_update(rule, grad, w32, st0, st1=None, wbf=None, corr=None, *, lr, a, oma, b, omb, eps,
+                 weight_decay, scale, lr_t=None):
+    """CPU reference of the HIP ``shard_update`` kernels: ``rule`` over one flat range, ``a`` /
+    ``oma`` / ``b`` / ``omb`` as ``ArenaOptHyper`` names them (RMSProp: rho, 1 - rho, momentum, -;
+    Adam: b1, 1 - b1, b2, 1 - b2; SGD: -, -, momentum, -). ``st0`` / ``st1``: RMSProp's ms / mom,
+    Adam's m / v, SGD's mom. With ``wbf`` the fp32 ``w32`` are masters and ``wbf`` receives the
+    rounded bf16 weights."""
+    if rule == OPT_SGD:
+        shard_sgd(grad, w32, st0, wbf, lr, b, weight_decay, scale, lr_t=lr_t)
+        return
+    g = grad.float()
+    if rule == OPT_RMSPROP:
+        _rmsprop(g, w32, st0, st1, _lr_value(lr, lr_t), a, oma, b, eps, weight_decay, scale)
+    elif rule == OPT_ADAM:
+        step = _f32(_lr_value(lr, lr_t)) * corr.reshape(())
+        _adam(g, w32, st0, st1, step, a, oma, b, omb, eps, weight_decay, scale)
+    else:
+        raise ValueError(f"shard_update: unknown rule {rule}")
+    if wbf is not None:
+        wbf.copy_(w32)
+
+
+# ------------------------------------------------------------------------------------------------
+# Sharded LARS (``ShardedMasterSGD(rule="lars")``): the definition above on the AVERAGED gradient
+# of data-parallel ranks, each of which holds a shard of the summed gradient after the
+# reduce-scatter. With ``scale = 1 / world`` and g the summed gradient:
+#
+#       d = g * scale (an fp32 product)       wn = ||w||2       gn = ||d||2
+#       trust, step as above
+#       m = mu * m + (d + wd * w)             w = w - step * m          wbf = bf16(w)
+#
+# A shard intersects several tensors; each intersection is a piece. ``shard_lars_norms`` gives the
+# fp64 sums of w^2 and d^2 over each piece of this rank (0.0 for tensors without one), the ranks
+# all-reduce the sums (every rank then holds the same bits, so the same trust), and
+# ``shard_lars_update`` forms ``wn`` / ``gn`` = ``float32(sqrt(sum))`` and steps its pieces.
+# ------------------------------------------------------------------------------------------------
+def shard_lars_norms(grad, master, goffs, moffs, ns, slots, sums, workspace, scale):
+    """CPU reference of the HIP ``shard_lars_norms`` kernels (``workspace`` is not used)."""
+    sums.zero_()
+    for go, mo, n, slot in zip(goffs, moffs, ns, slots):
+        sums[2 * slot] = _sum_squares(master[mo:mo + n])
+        sums[2 * slot + 1] = _sum_squares(grad[go:go + n].float() * _f32(scale))
+
+
+def shard_lars_update(grad, master, mom, wbf, goffs, moffs, ns, slots, sums, trust, lr, momentum,
+                      weight_decay, eeta, eps, scale, lr_t=None):
+    """CPU reference of the HIP ``shard_lars_update`` kernels: ``trust[s]`` for every tensor of the
+    sub-range from the (reduced) ``sums``, then ``shard_sgd``'s lines over the pieces with the
+    step ``lr * trust``."""
+    lr = _f32(_lr_value(lr, lr_t))
+    for s in range(trust.numel()):
+        trust[s] = lars_trust_of_sums(sums[2 * s], sums[2 * s + 1], eeta, weight_decay, eps)
+    for go, mo, n, slot in zip(goffs, moffs, ns, slots):
+        w, m = master[mo:mo + n], mom[mo:mo + n]
+        d = grad[go:go + n].float() * scale + weight_decay * w
+        m.mul_(momentum).add_(d)
+        w.sub_((lr * trust[slot]) * m)
+        wbf[mo:mo + n].copy_(w)
 
 
 # ------------------------------------------------------------------------------------------------

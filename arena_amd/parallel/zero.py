@@ -64,6 +64,19 @@ arrived (unused parameters: zero gradient, as Horovod) and joins the comm stream
 
 Masters and momentum are full-length arrays of which each rank updates only the chunks it
 owns; :meth:`state_dict` reassembles them.
+
+Other rules. On the RCCL and hier backends ``rule="rmsprop" | "adam" | "lars"`` replaces the
+shard's momentum SGD with TF1's RMSProp or Adam (``shard_update`` kernels; a second full-length
+state array; Adam's bias correction in one :class:`AdamClock`, ticked once per step on the comm
+stream ahead of the step's first bucket update) or with LARS. LARS needs each tensor's norms, and
+a shard cuts tensors: every rank sums w^2 and (g / W)^2 over the pieces of its shard
+(``shard_lars_norms``), one fp64 all-reduce of two numbers per tensor of the sub-range gives every
+rank the same sums, and ``shard_lars_update`` steps the pieces with the same trust ratios
+everywhere (``opt.trust``). The piece table of each (sub-range, rank) pair is built once, at
+construction; nothing in a step reads a device value on the host. The xGMI kernels fuse momentum
+SGD only: ``backend="xgmi"`` refuses the other rules and ``"auto"`` then skips it. A bf16
+sub-range whose reduce-scatter summed in fp32 (``rccl_reduce_fp32``) is updated in the wide
+layout: fp32 gradient, fp32 master, bf16 weight out.
 """
 from __future__ import annotations
 
@@ -74,13 +87,18 @@ from typing import Iterable, List, Optional
 import torch
 import torch.distributed as dist
 
-from ..ops.optim import _same_memory_order
+from ..ops.optim import (AdamClock, _non_negative, _positive, _same_memory_order,
+                         _unit_interval)
 from ..ops.schedule import DeviceLR, attach_state, restore_state
 from ..runtime import heartbeat
 
 Tensor = torch.Tensor
 _BF16, _F32 = torch.bfloat16, torch.float32
 _ALIGN = {_BF16: 8, _F32: 4}          # 16-byte slots
+_RULES = ("sgd", "rmsprop", "adam", "lars")
+# state_dict key of the second fp32 state buffer of the rules that keep two ("momentum_buffer"
+# holds RMSProp's momentum and Adam's first moment)
+_SECOND = {"rmsprop": "mean_square", "adam": "exp_avg_sq"}
 
 
 def _pad(n: int, a: int) -> int:
@@ -94,6 +112,26 @@ class _Range:
         self.dtype, self.gi = dtype, gi            # element dtype and param-group index
         self.params, self.offsets = params, offsets
         self.start, self.end = start, end          # region-relative, element units of `dtype`
+        self.lars = None                           # rule="lars": this rank's pieces (_LarsRange)
+
+
+class _LarsRange:
+    """What a LARS sub-range keeps for this rank: the pieces of its shard [lo, lo + sl) -- its
+    intersections with the sub-range's tensors: offset inside the shard, offset in the master
+    buffer, length, the tensor's index -- the fp64 sums the ranks all-reduce, and where the
+    tensors' trust ratios go."""
+
+    def __init__(self, r: "_Range", lo: int, sl: int, trust: Tensor, dev):
+        self.goffs, self.moffs, self.ns, self.slots = [], [], [], []
+        for slot, (p, off) in enumerate(zip(r.params, r.offsets)):
+            a, b = max(off, lo), min(off + p.numel(), lo + sl)
+            if a < b:
+                self.goffs.append(a - lo)
+                self.moffs.append(a)
+                self.ns.append(b - a)
+                self.slots.append(slot)
+        self.sums = torch.zeros(2 * len(r.params), dtype=torch.float64, device=dev)
+        self.trust = trust                         # this sub-range's slice of the trust buffer
 
 
 class _Bucket:
@@ -125,13 +163,50 @@ class ShardedMasterSGD:
     (registration) order, which decides the buckets (default: the param groups' order).
     ``lr``: a float, or a :class:`DeviceLR` on the parameters' device that the caller advances at
     the head of every step (see "Update timing" above); a group's own ``lr`` override stays a
-    float, groups without one read the device value."""
+    float, groups without one read the device value.
+
+    ``rule``: ``"sgd"`` (default: everything above), or on the RCCL / hier backends ``"rmsprop"``
+    (``decay``, ``eps`` = 1.0; its momentum is ``momentum``), ``"adam"`` (``betas``, ``eps`` =
+    1e-8, optionally a ``clock`` to read instead of owning one) or ``"lars"`` (``eeta``, ``eps`` =
+    0.0; a group's ``"lars": False``, and every fp32-weights group, keeps momentum SGD; a LARS
+    group needs bf16 weights with ``numel % 4 == 0``). ``decay`` / ``eps`` / ``eeta`` may be
+    overridden per group. ``state_dict`` then carries ``rule``, the second state
+    (``mean_square`` / ``exp_avg_sq``; ``momentum_buffer`` holds RMSProp's momentum and Adam's
+    first moment) and the clock; loading another rule's state raises."""
 
     def __init__(self, params: Iterable, lr, momentum: float = 0.0,
                  weight_decay: float = 0.0, bucket_mb: float = 16.0, group=None,
                  timeout_s: float = 60.0, overlap: bool = True, backend: str = "auto",
                  order: Optional[Iterable[Tensor]] = None, last_bucket_mb: Optional[float] = None,
-                 rccl_reduce_fp32: Optional[bool] = None, local_size: Optional[int] = None):
+                 rccl_reduce_fp32: Optional[bool] = None, local_size: Optional[int] = None,
+                 rule: str = "sgd", decay: float = 0.9, betas=(0.9, 0.999),
+                 eps: Optional[float] = None, eeta: float = 0.001,
+                 clock: Optional[AdamClock] = None):
+        if rule not in _RULES:
+            raise ValueError(f"rule must be one of {', '.join(_RULES)} (got {rule!r})")
+        if rule != "sgd" and backend == "xgmi":
+            raise ValueError(f"backend='xgmi' implements momentum SGD only: rule={rule!r} is not "
+                             "fused into the xGMI kernels; use backend 'rccl', 'hier' or 'auto'")
+        self.rule = rule
+        # the rule's hyperparameters, validated as ops/optim.py validates them; they join every
+        # param group (a group may override them), and rule="sgd" adds none
+        extra = {}
+        if rule == "rmsprop":
+            _unit_interval("momentum", momentum)
+            extra = {"decay": _unit_interval("decay", decay),
+                     "eps": _positive("eps", 1.0 if eps is None else eps)}
+        elif rule == "adam":
+            self._betas = (_unit_interval("beta1", betas[0]), _unit_interval("beta2", betas[1]))
+            if clock is not None and clock.betas != self._betas:
+                raise ValueError(f"betas {self._betas} differ from the shared AdamClock's "
+                                 f"{clock.betas}")
+            extra = {"eps": _positive("eps", 1e-8 if eps is None else eps)}
+        elif rule == "lars":
+            _unit_interval("momentum", momentum)
+            extra = {"eeta": _positive("eeta", eeta),
+                     "eps": _non_negative("eps", 0.0 if eps is None else eps)}
+        if clock is not None and rule != "adam":
+            raise ValueError("clock= belongs to rule='adam'")
         plist = list(params)
         if plist and isinstance(plist[0], dict):
             raw_groups = plist
@@ -150,6 +225,10 @@ class ShardedMasterSGD:
             self.param_groups.append({"params": ps, "lr": lr_g,
                                       "momentum": float(g.get("momentum", momentum)),
                                       "weight_decay": float(g.get("weight_decay", weight_decay))})
+            check = {"decay": _unit_interval, "eeta": _positive,
+                     "eps": _non_negative if rule == "lars" else _positive}
+            for k, v in extra.items():
+                self.param_groups[-1][k] = check[k](k, g.get(k, v))
         self.params: List[Tensor] = [p for g in self.param_groups for p in g["params"]]
         if not self.params:
             raise ValueError("ShardedMasterSGD needs at least one parameter")
@@ -175,6 +254,13 @@ class ShardedMasterSGD:
             if kind is None:
                 raise ValueError("param group 'weights' must be 'bf16' or 'fp32'")
             g["weights"] = "bf16" if kind == _BF16 else "fp32"
+            if rule == "lars":
+                # as TFLars: groups with lars=False (and every fp32-weights group: BN scales /
+                # shifts, biases -- LARS's skip list) take plain momentum SGD
+                g["lars"] = bool(raw_groups[gi].get("lars", kind == _BF16))
+                if g["lars"] and (kind != _BF16 or any(p.numel() % 4 for p in g["params"])):
+                    raise ValueError("a LARS param group needs bf16 weights and numel % 4 == 0 "
+                                     "for every parameter (set 'lars': False for the others)")
             for p in g["params"]:
                 kind_of[id(p)] = (kind, gi)
                 if p.device != dev:
@@ -191,7 +277,9 @@ class ShardedMasterSGD:
         self.local_size = self._local_size(local_size, strict=backend == "hier")
         if backend == "auto":
             from . import xgmi
-            backend = "xgmi" if dev.type == "cuda" and xgmi.usable(group) else self._flat_or_hier()
+            # the xGMI kernels fuse momentum SGD only: the other rules go over RCCL
+            backend = ("xgmi" if rule == "sgd" and dev.type == "cuda" and xgmi.usable(group)
+                       else self._flat_or_hier())
         self._intra = self._inter = None
         if backend == "hier":
             self._make_level_groups()
@@ -237,6 +325,23 @@ class ShardedMasterSGD:
         self.master = torch.zeros(self.t16, dtype=_F32, device=dev)
         self.mom = torch.zeros(self.t16, dtype=_F32, device=dev)
         self.mom32 = torch.zeros(self.t32, dtype=_F32, device=dev)
+        # the second state of the rules that keep two: RMSProp's mean square (it starts at 1.0 as
+        # TF's slot does; mom / mom32 are its momentum), Adam's second moment (mom / mom32: first)
+        self.aux = self.aux32 = None
+        if rule in _SECOND:
+            init = 1.0 if rule == "rmsprop" else 0.0
+            self.aux = torch.full((self.t16,), init, dtype=_F32, device=dev)
+            self.aux32 = torch.full((self.t32,), init, dtype=_F32, device=dev)
+        self.clock = None
+        self._owns_clock = clock is None
+        self._ticked = False    # Adam: the clock has been ticked for the step in flight
+        if rule == "adam":
+            if clock is not None and clock.device != dev:
+                raise ValueError(f"the AdamClock lives on {clock.device}, the parameters on "
+                                 f"{dev}")
+            self.clock = AdamClock(self._betas, dev) if clock is None else clock
+        if rule == "lars":
+            self._make_lars_ranges()
         self._owner = {}
         with torch.no_grad():
             wbuf.zero_()
@@ -377,6 +482,37 @@ class ShardedMasterSGD:
         m32 = self._max_range_elems(_F32) // max(1, self.world)
         return max(4, m16 if self.rccl_reduce_fp32 else (m16 + 1) // 2, m32)
 
+    def _make_lars_ranges(self) -> None:
+        """rule="lars": the piece table of every (LARS sub-range, this rank) pair, built once; the
+        trust ratios of all LARS tensors in one buffer (sub-range by sub-range, so a sub-range's
+        kernels write one slice of it) and the workspace of the norm kernels' partial sums."""
+        from ..ops import fused
+        ranges = [r for b in self.buckets for r in b.ranges
+                  if r.dtype == _BF16 and self.param_groups[r.gi]["lars"]]
+        total = sum(len(r.params) for r in ranges)
+        self._trust = torch.ones(total, dtype=_F32, device=self.device)
+        base, order, words = 0, {}, 4
+        for r in ranges:
+            sl = (r.end - r.start) // self.world
+            lo = r.start + self._shard_index(self.rank) * sl
+            r.lars = _LarsRange(r, lo, sl, self._trust[base:base + len(r.params)], self.device)
+            for i, p in enumerate(r.params):
+                order[id(p)] = base + i
+            base += len(r.params)
+            words = max(words, fused.mt_lars_workspace_floats(r.lars.ns))
+        self._lars_ws = torch.empty(words, dtype=_F32, device=self.device)
+        # opt.trust lists the LARS parameters in the optimizer's parameter order
+        self._trust_perm = torch.tensor([order[id(p)] for p in self.params if id(p) in order],
+                                        dtype=torch.int64, device=self.device)
+
+    @property
+    def trust(self) -> Tensor:
+        """rule="lars": the trust ratios of the last step, one fp32 entry per LARS parameter in
+        parameter order (1.0 until the first update); derived, not state. No host read."""
+        if self.rule != "lars":
+            raise AttributeError("trust belongs to rule='lars'")
+        return self._trust[self._trust_perm]
+
     # ----------------------------------------------------------------------------------------
     @staticmethod
     def _view(flat: Tensor, p: Tensor, off: int) -> Tensor:
@@ -410,6 +546,11 @@ class ShardedMasterSGD:
                     src.append(gr)
             if dst:
                 torch._foreach_copy_(dst, src)
+            if self.clock is not None and self._owns_clock and not self._ticked:
+                # Adam: one tick per step, on the comm stream, ahead of the step's first bucket
+                # update; a launch, not a host read. Every rank ticks alike.
+                self.clock.tick()
+                self._ticked = True
             for r in b.ranges:
                 g = self.param_groups[r.gi]
                 lr, mu, wd = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
@@ -446,16 +587,57 @@ class ShardedMasterSGD:
             else:
                 out = self._rs_out.view(_BF16)[:sl]
                 self._reduce_scatter(out, self.stage[r.start:r.end])
-            fused.shard_sgd(out, self.master[lo:lo + sl], self.mom[lo:lo + sl],
-                            self.wbf[lo:lo + sl], lr=lr, momentum=mu, weight_decay=wd,
-                            scale=scale, lr_t=lr_t)
+            if self.rule == "sgd":
+                fused.shard_sgd(out, self.master[lo:lo + sl], self.mom[lo:lo + sl],
+                                self.wbf[lo:lo + sl], lr=lr, momentum=mu, weight_decay=wd,
+                                scale=scale, lr_t=lr_t)
+            else:
+                self._shard_rule(r, out, lo, sl, lr, mu, wd, lr_t)
             self._all_gather(self.wbf, r.start, n, lo, sl)
         else:
             out = self._rs_out[:sl]
             self._reduce_scatter(out, self.stage32[r.start:r.end])
-            fused.shard_sgd(out, self.w32[lo:lo + sl], self.mom32[lo:lo + sl], None, lr=lr,
-                            momentum=mu, weight_decay=wd, scale=scale, lr_t=lr_t)
+            if self.rule == "sgd":
+                fused.shard_sgd(out, self.w32[lo:lo + sl], self.mom32[lo:lo + sl], None, lr=lr,
+                                momentum=mu, weight_decay=wd, scale=scale, lr_t=lr_t)
+            else:
+                self._shard_rule(r, out, lo, sl, lr, mu, wd, lr_t)
             self._all_gather(self.w32, r.start, n, lo, sl)
+
+    def _shard_rule(self, r: _Range, out: Tensor, lo: int, sl: int, lr, mu, wd, lr_t) -> None:
+        """The shard update of rule rmsprop / adam / lars on the reduce-scattered ``out`` (bf16,
+        or fp32: an fp32 sub-range, or a bf16 one summed in fp32 -- the wide layout)."""
+        from ..ops import fused
+        g = self.param_groups[r.gi]
+        scale = 1.0 / self.world
+        bf = r.dtype == _BF16
+        w = (self.master if bf else self.w32)[lo:lo + sl]
+        st = (self.mom if bf else self.mom32)[lo:lo + sl]
+        wb = self.wbf[lo:lo + sl] if bf else None
+        if self.rule == "rmsprop":
+            ms = (self.aux if bf else self.aux32)[lo:lo + sl]
+            fused.shard_rmsprop(out, w, ms, st, wb, lr=lr, decay=g["decay"], momentum=mu,
+                                eps=g["eps"], weight_decay=wd, scale=scale, lr_t=lr_t)
+        elif self.rule == "adam":
+            v = (self.aux if bf else self.aux32)[lo:lo + sl]
+            fused.shard_adam(out, w, st, v, self.clock.corr, wb, lr=lr, betas=self.clock.betas,
+                             eps=g["eps"], weight_decay=wd, scale=scale, lr_t=lr_t)
+        elif r.lars is None:
+            # LARS's skip list (fp32 weights, groups with lars=False): plain momentum SGD
+            fused.shard_sgd(out, w, st, wb, lr=lr, momentum=mu, weight_decay=wd, scale=scale,
+                            lr_t=lr_t)
+        else:
+            # per-tensor norms need every rank's pieces: this rank's fp64 sums, one all-reduce
+            # over the whole group (two entries per tensor), then the update with the same
+            # trust ratios on every rank
+            t = r.lars
+            fused.shard_lars_norms(out, self.master, t.goffs, t.moffs, t.ns, t.slots, t.sums,
+                                   self._lars_ws, scale=scale)
+            if self.world > 1:
+                dist.all_reduce(t.sums, group=self.group)
+            fused.shard_lars_update(out, self.master, self.mom, self.wbf, t.goffs, t.moffs, t.ns,
+                                    t.slots, t.sums, t.trust, lr=lr, momentum=mu, weight_decay=wd,
+                                    eeta=g["eeta"], eps=g["eps"], scale=scale, lr_t=lr_t)
 
     def _reduce_scatter(self, out: Tensor, inp: Tensor) -> None:
         if self._intra is None:
@@ -523,6 +705,7 @@ class ShardedMasterSGD:
             b.launched = False
             b.pending = set(id(p) for p in b.params)
         self._next = 0
+        self._ticked = False
 
     # ------------------------------------------------------------------------- optimizer API
     @contextlib.contextmanager
@@ -552,6 +735,7 @@ class ShardedMasterSGD:
             b.launched = False
             b.pending = set(id(p) for p in b.params)
         self._next = 0
+        self._ticked = False
         heartbeat.beat()
         return None
 
@@ -613,11 +797,29 @@ class ShardedMasterSGD:
                  "shapes": [tuple(p.shape) for p in self.params],
                  "param_groups": [{k: v for k, v in g.items() if k != "params"}
                                   for g in self.param_groups]}
+        if self.rule != "sgd":
+            state["rule"] = self.rule
+        if self.rule in _SECOND:
+            aux = self._gathered(self.aux, _BF16) if self.t16 else self.aux
+            aux32 = self._gathered(self.aux32, _F32) if self.t32 else self.aux32
+            state[_SECOND[self.rule]] = [self._logical(aux if p.dtype == _BF16 else aux32, p)
+                                         for p in self.params]
+        if self.clock is not None:
+            state["clock"] = self.clock.state_dict()
         return attach_state(state, self.lr_sched)
 
     @torch.no_grad()
     def load_state_dict(self, state: dict) -> None:
+        if state.get("rule", "sgd") != self.rule:
+            raise ValueError(f"ShardedMasterSGD(rule={self.rule!r}) cannot load the state of "
+                             f"rule {state.get('rule', 'sgd')!r}")
         masters, moms = state["master"], state["momentum_buffer"]
+        seconds = state[_SECOND[self.rule]] if self.rule in _SECOND else None
+        if seconds is not None and (isinstance(seconds, Tensor) or len(seconds) != len(self.params)
+                                    or any(tuple(a.shape) != tuple(p.shape)
+                                           for a, p in zip(seconds, self.params))):
+            raise ValueError(f"ShardedMasterSGD state: {_SECOND[self.rule]} must hold one tensor "
+                             "of each parameter's shape")
         if isinstance(masters, Tensor) or isinstance(moms, Tensor):
             raise ValueError("ShardedMasterSGD state must hold one tensor per parameter")
         n = len(self.params)
@@ -642,10 +844,15 @@ class ShardedMasterSGD:
             else:
                 self._view(self.w32, p, o).copy_(a)
                 self._view(self.mom32, p, o).copy_(b)
+        for p, a in zip(self.params, seconds or []):
+            self._view(self.aux if p.dtype == _BF16 else self.aux32, p,
+                       self.offsets[id(p)]).copy_(a)
         for g, st in zip(self.param_groups, groups or []):
-            for k in ("lr", "momentum", "weight_decay"):
-                if k in st:
+            for k in ("lr", "momentum", "weight_decay", "decay", "eps", "eeta"):
+                if k in st and k in g:
                     g[k] = float(st[k])
+        if self.clock is not None:
+            self.clock.load_state_dict(state["clock"])
         restore_state(state, self.lr_sched)
         self._rebind()
 

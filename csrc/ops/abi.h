@@ -285,6 +285,32 @@ hipError_t arena_mt_update_f32(int rule, const float* const* grads, const long l
 hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* mom, void* wbf,
                            long long n, float lr, const float* lr_ptr, float mu, float wd,
                            float scale, hipStream_t stream);
+// `rule` over one flat range (a data-parallel rank's shard), n % 4 == 0, pointers aligned as for
+// arena_shard_sgd, grid-stride with the same 4096-block cap. Layouts: bf16 grad + wbf (fp32 master,
+// bf16 weights written); fp32 grad without wbf (fp32 weights are their own masters); fp32 grad +
+// wbf (wide: fp32 master, bf16 weights written). RMSProp / Adam (st1; Adam: hyper.corr) in all
+// three, SGD (st1 unused) in the wide layout only; anything else is hipErrorInvalidValue.
+hipError_t arena_shard_update(int rule, const void* grad, int grad_bf16, float* w32, float* st0,
+                              float* st1, void* wbf /*nullable*/, long long n, ArenaOptHyper hyper,
+                              hipStream_t stream);
+// Sharded LARS. A shard's pieces: piece i is ns[i] elements (a multiple of 4) at grad + goffs[i]
+// (bf16 or fp32 summed gradient) and master + moffs[i], of tensor slots[i] in [0, n_slots).
+//   _norms:  sums[2 s] / sums[2 s + 1] = fp64 sums of w^2 / (g * scale)^2 over this rank's piece of
+//            tensor s, 0.0 without one (all 2 * n_slots written; no atomics, fixed order).
+//            workspace: arena_mt_lars_workspace_floats(ns, count) floats, never read before written.
+//   -- the caller all-reduces sums (SUM) over the ranks that share the tensors --
+//   _update: trust[s] for every s from the reduced sums (as arena_mt_lars_master forms it), then
+//            d = g * scale + wd * w; m = mu * m + d; w -= lr * trust * m over the pieces, rounded
+//            bf16 weights to wbf. hyper: the LARS column and scale.
+hipError_t arena_shard_lars_norms(const void* grad, int grad_bf16, const long long* goffs,
+                                  const long long* moffs, const long long* ns, const int* slots,
+                                  int count, int n_slots, const float* master, float scale,
+                                  float* workspace, double* sums, hipStream_t stream);
+hipError_t arena_shard_lars_update(const void* grad, int grad_bf16, const long long* goffs,
+                                   const long long* moffs, const long long* ns, const int* slots,
+                                   int count, int n_slots, float* master, float* mom, void* wbf,
+                                   const double* sums, float* trust, ArenaOptHyper hyper,
+                                   hipStream_t stream);
 // lr[0] = value of the piecewise-linear schedule seg[n_seg][4] (begin, end, lr0 bits, lr1 bits;
 // fp64 values as int64 bit patterns) at *step, then *step += 1.
 hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,

@@ -866,6 +866,177 @@ void shard_sgd(Tensor grad, Tensor w32, Tensor mom, c10::optional<Tensor> wbf, d
             "shard_sgd");
 }
 
+// What a shard update's range must be (shard_sgd's checks): dense fp32 w32 and states of one size,
+// a multiple of 4, 16-byte aligned; a bf16 (8-byte aligned) or fp32 gradient of that size; wbf, when
+// given, a dense 8-byte aligned bf16 range of that size; all on one GPU. Returns wbf's pointer.
+void* shard_range(const Tensor& grad, const Tensor& w32, const std::vector<Tensor>& states,
+                  const c10::optional<Tensor>& wbf, const char* what) {
+  check_f32(w32, "w32");
+  check_dev(grad, "grad");
+  const bool bf = grad.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf || grad.scalar_type() == torch::kFloat32, what, ": grad must be bf16 or fp32");
+  const int64_t n = w32.numel();
+  TORCH_CHECK(grad.is_contiguous() && w32.is_contiguous() && grad.device() == w32.device(), what,
+              ": contiguous tensors on one GPU");
+  TORCH_CHECK(grad.numel() == n && n % 4 == 0, what, ": equal sizes, a multiple of 4");
+  TORCH_CHECK(aligned_to(w32, 16) && aligned_to(grad, bf ? 8 : 16), what, ": misaligned range");
+  for (const Tensor& st : states) {
+    check_f32(st, "state");
+    TORCH_CHECK(st.is_contiguous() && st.device() == w32.device(), what,
+                ": contiguous tensors on one GPU");
+    TORCH_CHECK(st.numel() == n, what, ": equal sizes, a multiple of 4");
+    TORCH_CHECK(aligned_to(st, 16), what, ": misaligned range");
+  }
+  if (!wbf.has_value()) {
+    TORCH_CHECK(!bf, what, ": bf16 gradients need the bf16 weight range");
+    return nullptr;
+  }
+  check_dev(*wbf, "wbf");
+  TORCH_CHECK(wbf->scalar_type() == torch::kBFloat16 && wbf->is_contiguous() &&
+                  wbf->numel() == n && wbf->device() == w32.device() && aligned_to(*wbf, 8),
+              what, ": wbf must be a dense, 8-byte aligned bf16 range of the same size");
+  return wbf->data_ptr();
+}
+
+// The rule family over one flat range (a rank's shard), by `rule` (ARENA_OPT_*) and ArenaOptHyper's
+// column for it (a / oma / b / omb as the struct names them). SGD: the wide layout only (fp32
+// gradient with wbf); shard_sgd keeps the other two.
+void shard_update(int64_t rule, Tensor grad, Tensor w32, Tensor st0, c10::optional<Tensor> st1,
+                  c10::optional<Tensor> wbf, c10::optional<Tensor> corr, double lr, double a,
+                  double oma, double b, double omb, double eps, double weight_decay, double scale,
+                  OptT lr_t) {
+  const char* what = "shard_update";
+  TORCH_CHECK(rule == ARENA_OPT_SGD || rule == ARENA_OPT_RMSPROP || rule == ARENA_OPT_ADAM, what,
+              ": unknown rule ", rule);
+  std::vector<Tensor> states{st0};
+  if (st1.has_value()) states.push_back(*st1);
+  void* wp = shard_range(grad, w32, states, wbf, what);
+  const bool bf = grad.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(rule == ARENA_OPT_SGD || st1.has_value(), what,
+              ": RMSProp and Adam keep a second state buffer (st1)");
+  TORCH_CHECK(rule != ARENA_OPT_SGD || (!bf && wp), what,
+              ": SGD runs here in the wide layout only (fp32 gradient with wbf); shard_sgd has "
+              "the others");
+  ArenaOptHyper h = opt_hyper(lr, lr_t, w32, weight_decay, scale, what);
+  h.a = (float)a;
+  h.oma = (float)oma;
+  h.b = (float)b;
+  h.omb = (float)omb;
+  h.eps = (float)eps;
+  if (rule == ARENA_OPT_ADAM) {
+    TORCH_CHECK(corr.has_value(), what, ": Adam needs corr (the AdamClock's bias correction)");
+    h.corr = corr_ptr(*corr, w32, what);
+  }
+  check_hip(arena_shard_update((int)rule, grad.data_ptr(), bf ? 1 : 0, w32.data_ptr<float>(),
+                               st0.data_ptr<float>(),
+                               st1.has_value() ? st1->data_ptr<float>() : nullptr, wp,
+                               w32.numel(), h, cur_stream()),
+            what);
+}
+
+// A shard's LARS pieces, checked against the gradient shard and the master buffer.
+struct ShardPieces {
+  std::vector<long long> goffs, moffs, ns;
+  std::vector<int> slots;
+};
+
+ShardPieces shard_pieces(const Tensor& grad, const Tensor& master,
+                         const std::vector<int64_t>& goffs, const std::vector<int64_t>& moffs,
+                         const std::vector<int64_t>& ns, const std::vector<int64_t>& slots,
+                         int64_t n_slots, const char* what) {
+  check_f32(master, "master");
+  check_dev(grad, "grad");
+  const bool bf = grad.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(bf || grad.scalar_type() == torch::kFloat32, what, ": grad must be bf16 or fp32");
+  TORCH_CHECK(grad.is_contiguous() && master.is_contiguous() && grad.device() == master.device(),
+              what, ": contiguous tensors on one GPU");
+  TORCH_CHECK(aligned_to(master, 16) && aligned_to(grad, bf ? 8 : 16), what,
+              ": misaligned range");
+  TORCH_CHECK(goffs.size() == ns.size() && moffs.size() == ns.size() && slots.size() == ns.size(),
+              what, ": goffs, moffs, ns and slots must have one entry per piece");
+  TORCH_CHECK(n_slots >= 0 && n_slots < (1 << 30), what, ": n_slots out of range");
+  ShardPieces p;
+  std::vector<char> seen((size_t)n_slots, 0);
+  for (size_t i = 0; i < ns.size(); ++i) {
+    TORCH_CHECK(ns[i] >= 0 && ns[i] % 4 == 0 && goffs[i] >= 0 && goffs[i] % 4 == 0 &&
+                    moffs[i] >= 0 && moffs[i] % 4 == 0 && goffs[i] + ns[i] <= grad.numel() &&
+                    moffs[i] + ns[i] <= master.numel(),
+                what, ": piece ", i, " misaligned or out of bounds");
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < n_slots, what, ": slot ", i, " (", slots[i],
+                ") out of range of the sub-range's ", n_slots, " tensors");
+    TORCH_CHECK(!seen[(size_t)slots[i]], what, ": slot ", slots[i], " names two pieces");
+    seen[(size_t)slots[i]] = 1;
+    p.goffs.push_back(goffs[i]);
+    p.moffs.push_back(moffs[i]);
+    p.ns.push_back(ns[i]);
+    p.slots.push_back((int)slots[i]);
+  }
+  return p;
+}
+
+void shard_lars_norms(Tensor grad, Tensor master, std::vector<int64_t> goffs,
+                      std::vector<int64_t> moffs, std::vector<int64_t> ns,
+                      std::vector<int64_t> slots, Tensor sums, Tensor workspace, double scale) {
+  const char* what = "shard_lars_norms";
+  const int64_t n_slots = sums.numel() / 2;
+  const ShardPieces p = shard_pieces(grad, master, goffs, moffs, ns, slots, n_slots, what);
+  check_dev(sums, "sums");
+  check_f32(workspace, "workspace");
+  TORCH_CHECK(sums.scalar_type() == torch::kFloat64 && sums.is_contiguous() &&
+                  sums.numel() % 2 == 0,
+              what, ": sums must be a dense float64 range of 2 entries per tensor");
+  TORCH_CHECK(sums.device() == master.device() && workspace.device() == master.device(), what,
+              ": sums and workspace must be on the master buffer's GPU");
+  const long long need = arena_mt_lars_workspace_floats(p.ns.data(), (int)p.ns.size());
+  TORCH_CHECK(aligned_to(workspace, 16), what, ": workspace must be 16-byte aligned");
+  TORCH_CHECK(workspace.numel() >= need, what, ": workspace holds ", workspace.numel(),
+              " floats, these pieces' blocks need ", need);
+  check_hip(arena_shard_lars_norms(grad.data_ptr(), grad.scalar_type() == torch::kBFloat16,
+                                   p.goffs.data(), p.moffs.data(), p.ns.data(), p.slots.data(),
+                                   (int)p.ns.size(), (int)n_slots, master.data_ptr<float>(),
+                                   (float)scale, workspace.data_ptr<float>(),
+                                   sums.data_ptr<double>(), cur_stream()),
+            what);
+}
+
+void shard_lars_update(Tensor grad, Tensor master, Tensor mom, Tensor wbf,
+                       std::vector<int64_t> goffs, std::vector<int64_t> moffs,
+                       std::vector<int64_t> ns, std::vector<int64_t> slots, Tensor sums,
+                       Tensor trust, double lr, double momentum, double weight_decay, double eeta,
+                       double eps, double scale, OptT lr_t) {
+  const char* what = "shard_lars_update";
+  const int64_t n_slots = trust.numel();
+  const ShardPieces p = shard_pieces(grad, master, goffs, moffs, ns, slots, n_slots, what);
+  check_f32(mom, "mom");
+  check_dev(wbf, "wbf");
+  check_dev(sums, "sums");
+  check_f32(trust, "trust");
+  TORCH_CHECK(mom.numel() == master.numel() && mom.is_contiguous() && aligned_to(mom, 16) &&
+                  wbf.scalar_type() == torch::kBFloat16 && wbf.numel() == master.numel() &&
+                  wbf.is_contiguous() && aligned_to(wbf, 8),
+              what, ": flat buffers must be fp32 (master, mom) and bf16 (wbf) of equal size, "
+              "16-byte (wbf: 8-byte) aligned");
+  TORCH_CHECK(sums.scalar_type() == torch::kFloat64 && sums.is_contiguous() &&
+                  sums.numel() == 2 * n_slots && trust.is_contiguous(),
+              what, ": sums must be float64 with 2 entries per entry of trust");
+  TORCH_CHECK(mom.device() == master.device() && wbf.device() == master.device() &&
+                  sums.device() == master.device() && trust.device() == master.device(),
+              what, ": every tensor must be on the master buffer's GPU");
+  ArenaOptHyper h = opt_hyper(lr, lr_t, master, weight_decay, scale, what);
+  h.a = (float)eeta;
+  h.b = (float)momentum;
+  h.eps = (float)eps;
+  TORCH_CHECK(h.a > 0.f, what, ": eeta must be > 0");
+  TORCH_CHECK(h.eps >= 0.f, what, ": eps must be >= 0");
+  check_hip(arena_shard_lars_update(grad.data_ptr(), grad.scalar_type() == torch::kBFloat16,
+                                    p.goffs.data(), p.moffs.data(), p.ns.data(), p.slots.data(),
+                                    (int)p.ns.size(), (int)n_slots, master.data_ptr<float>(),
+                                    mom.data_ptr<float>(), wbf.data_ptr(),
+                                    sums.data_ptr<double>(), trust.data_ptr<float>(), h,
+                                    cur_stream()),
+            what);
+}
+
 // ------------------------------------------------------------------------------ xGMI collective
 int64_t ccl_malloc(int64_t bytes, bool uncached) {
   TORCH_CHECK(bytes > 0, "ccl_malloc: bytes must be positive");
@@ -2452,6 +2623,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("shard_sgd", &shard_sgd, py::arg("grad"), py::arg("w32"), py::arg("mom"),
         py::arg("wbf") = py::none(), py::arg("lr"), py::arg("momentum"),
         py::arg("weight_decay"), py::arg("scale"), py::arg("lr_t") = py::none());
+  m.def("shard_update", &shard_update, py::arg("rule"), py::arg("grad"), py::arg("w32"),
+        py::arg("st0"), py::arg("st1") = py::none(), py::arg("wbf") = py::none(),
+        py::arg("corr") = py::none(), py::arg("lr"), py::arg("a"), py::arg("oma"), py::arg("b"),
+        py::arg("omb"), py::arg("eps"), py::arg("weight_decay"), py::arg("scale"),
+        py::arg("lr_t") = py::none());
+  m.def("shard_lars_norms", &shard_lars_norms, py::arg("grad"), py::arg("master"),
+        py::arg("goffs"), py::arg("moffs"), py::arg("ns"), py::arg("slots"), py::arg("sums"),
+        py::arg("workspace"), py::arg("scale"));
+  m.def("shard_lars_update", &shard_lars_update, py::arg("grad"), py::arg("master"),
+        py::arg("mom"), py::arg("wbf"), py::arg("goffs"), py::arg("moffs"), py::arg("ns"),
+        py::arg("slots"), py::arg("sums"), py::arg("trust"), py::arg("lr"), py::arg("momentum"),
+        py::arg("weight_decay"), py::arg("eeta"), py::arg("eps"), py::arg("scale"),
+        py::arg("lr_t") = py::none());
   m.def("ccl_malloc", &ccl_malloc);
   m.def("ccl_free", &ccl_free);
   m.def("ccl_memset", &ccl_memset);

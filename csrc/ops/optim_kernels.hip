@@ -9,6 +9,9 @@
 //   mt_f32<RULE>           multi-tensor update, fp32 layout: fp32 gradients and weights, any sizes
 //   mt_lars_norms/_update  LARS over the master layout: per-tensor norms, then mt_master's SGD
 //   shard_sgd<BF16>        momentum SGD over one flat range, either layout
+//   shard_update<RULE, L>  RMSProp / Adam over one flat range in the master, fp32 or wide layout
+//                          (fp32 gradient, fp32 master, bf16 weights written); SGD in the wide one
+//   shard_lars_*           LARS over the pieces of a rank's shard: norms, [all-reduce], update
 //   lr_schedule, adam_tick the learning-rate schedule and Adam's bias correction, on the device
 //
 // The multi-tensor kernels share ONE walk (mt_chunk: which tensor owns this 1024-element chunk),
@@ -19,6 +22,7 @@
 #include "adam.h"
 
 #include <algorithm>
+#include <vector>
 
 using namespace arena;
 
@@ -356,6 +360,65 @@ __global__ __launch_bounds__(256) void shard_sgd_kernel(const void* __restrict__
   }
 }
 
+// Wide layout, one thread's 4 elements: fp32 gradient (a reduce-scatter that summed in fp32), fp32
+// master and states, rounded bf16 weights written. master_update4 with a 16-byte gradient load.
+template <class RULE>
+__device__ __forceinline__ void wide_update4(const float* g, float* w, float* s0, float* s1,
+                                             uint16_t* wbf, float step, const ArenaOptHyper& h) {
+  const float4 g4 = *reinterpret_cast<const float4*>(g);
+  float4 w4 = *reinterpret_cast<const float4*>(w);
+  float4 p4 = *reinterpret_cast<const float4*>(s0);
+  float4 q4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (RULE::kStates == 2) q4 = *reinterpret_cast<const float4*>(s1);
+  const float* gf = &g4.x;
+  float* wf = &w4.x;
+  float* p = &p4.x;
+  float* q = &q4.x;
+  uint32_t r[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    RULE::apply(gf[k], wf[k], p[k], q[k], step, h);
+    r[k] = f32_to_bf16(wf[k]);
+  }
+  *reinterpret_cast<float4*>(w) = w4;
+  *reinterpret_cast<float4*>(s0) = p4;
+  if constexpr (RULE::kStates == 2) *reinterpret_cast<float4*>(s1) = q4;
+  *reinterpret_cast<uint2*>(wbf) = bf16x4_pack(r);
+}
+
+// The three layouts of a shard update: what the reduce-scatter left, and where the weights go.
+enum { SHARD_MASTER = 0,  // bf16 gradient, fp32 master and states, bf16 weights written
+       SHARD_F32 = 1,     // fp32 gradient, the fp32 weights are their own masters
+       SHARD_WIDE = 2 };  // fp32 gradient, fp32 master and states, bf16 weights written
+
+template <class RULE, int LAYOUT>
+__device__ __forceinline__ void shard_update4(const void* grad, long long gj, float* w, float* s0,
+                                              float* s1, uint16_t* wbf, float step,
+                                              const ArenaOptHyper& h) {
+  if constexpr (LAYOUT == SHARD_MASTER)
+    master_update4<RULE>(reinterpret_cast<const uint16_t*>(grad) + gj, w, s0, s1, wbf, step, h);
+  else if constexpr (LAYOUT == SHARD_F32)
+    f32_update4<RULE>(reinterpret_cast<const float*>(grad) + gj, w, s0, s1, step, h);
+  else
+    wide_update4<RULE>(reinterpret_cast<const float*>(grad) + gj, w, s0, s1, wbf, step, h);
+}
+
+// RULE over ONE flat range in one of the three layouts: shard_sgd_kernel's grid-stride walk (one
+// thread owns 4 elements per step; n % 4 == 0 and aligned pointers, host-checked) for the rules
+// and the layout it does not know. A rule with one state never touches st1.
+template <class RULE, int LAYOUT>
+__global__ __launch_bounds__(256) void shard_update_kernel(const void* __restrict__ grad,
+                                                           float* __restrict__ w32,
+                                                           float* __restrict__ st0,
+                                                           float* __restrict__ st1,
+                                                           uint16_t* __restrict__ wbf, long long n,
+                                                           ArenaOptHyper h) {
+  const float step = opt_step_size<RULE>(h);
+  const long long stride = (long long)gridDim.x * 1024;
+  for (long long j = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; j < n; j += stride)
+    shard_update4<RULE, LAYOUT>(grad, j, w32 + j, st0 + j, st1 + j, wbf + j, step, h);
+}
+
 // The learning-rate schedule of arena_amd/ops/schedule.py, advanced on the device so a captured
 // step changes its lr from replay to replay. One lane: finds the segment of *step by a linear
 // search over the (at most 64) segments, evaluates it in fp64 exactly as reference_lr does (every
@@ -431,6 +494,49 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// trust = eeta * wn / ((gn + wd * wn) + eps), 1 when a norm is 0: fp32 operations in the
+// reference's order; as in lr_schedule_kernel, the empty asm keeps -ffp-contract=fast from fusing
+// a product into the sum that follows it.
+__device__ __forceinline__ float lars_trust(float wn, float gn, const ArenaOptHyper& h) {
+  float trust = 1.f;
+  if (wn > 0.f && gn > 0.f) {
+    float num = h.a * wn;
+    float dec = h.wd * wn;
+    asm volatile("" : "+v"(num));
+    asm volatile("" : "+v"(dec));
+    trust = num / ((gn + dec) + h.eps);
+  }
+  return trust;
+}
+
+// A block's fp64 sums of `nb` (w^2, g^2) partials: lane t takes partials t, t + 256, ... in index
+// order (4 loads in flight), then the wave64 xor tree, then the four waves in order. Every block
+// that runs it over the same partials holds the same bits. red: 8 doubles of LDS.
+__device__ __forceinline__ void block_sum_pairs(const float2* __restrict__ p, int nb, double* red,
+                                                double& sw_out, double& sg_out) {
+  double sw = 0.0, sg = 0.0;
+  for (int i = threadIdx.x; i < nb; i += 1024) {
+    float2 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      v[k] = i + k * 256 < nb ? p[i + k * 256] : make_float2(0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      sw += (double)v[k].x;
+      sg += (double)v[k].y;
+    }
+  }
+  sw = wave_sum_f64(sw);
+  sg = wave_sum_f64(sg);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sw;
+    red[4 + (threadIdx.x >> 6)] = sg;
+  }
+  __syncthreads();
+  sw_out = ((red[0] + red[1]) + red[2]) + red[3];
+  sg_out = ((red[4] + red[5]) + red[6]) + red[7];
+}
+
 __global__ __launch_bounds__(256) void mt_lars_norms_kernel(MtArgs a, LarsSlots s,
                                                             const float* __restrict__ master,
                                                             float2* __restrict__ part) {
@@ -481,38 +587,11 @@ __global__ __launch_bounds__(256) void mt_lars_update_kernel(
   j += threadIdx.x * 4;
   const int first = a.blk_begin[ti];
   const int nb = a.blk_begin[ti + 1] - first;
-  const float2* p = part + s.part_base + first;
-  double sw = 0.0, sg = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 1024) {  // 4 loads in flight, summed in index order
-    float2 v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      v[k] = i + k * 256 < nb ? p[i + k * 256] : make_float2(0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      sw += (double)v[k].x;
-      sg += (double)v[k].y;
-    }
-  }
-  sw = wave_sum_f64(sw);
-  sg = wave_sum_f64(sg);
-  if ((threadIdx.x & 63) == 0) {
-    red[threadIdx.x >> 6] = sw;
-    red[4 + (threadIdx.x >> 6)] = sg;
-  }
-  __syncthreads();
-  const float wn = (float)sqrt(((red[0] + red[1]) + red[2]) + red[3]);
-  const float gn = (float)sqrt(((red[4] + red[5]) + red[6]) + red[7]);
-  float trust = 1.f;
-  if (wn > 0.f && gn > 0.f) {
-    // fp32 operations in the reference's order; as in lr_schedule_kernel, the empty asm keeps
-    // -ffp-contract=fast from fusing a product into the sum that follows it
-    float num = h.a * wn;
-    float dec = h.wd * wn;
-    asm volatile("" : "+v"(num));
-    asm volatile("" : "+v"(dec));
-    trust = num / ((gn + dec) + h.eps);
-  }
+  double sw, sg;
+  block_sum_pairs(part + s.part_base + first, nb, red, sw, sg);
+  const float wn = (float)sqrt(sw);
+  const float gn = (float)sqrt(sg);
+  const float trust = lars_trust(wn, gn, h);
   float step = lr * trust;
   asm volatile("" : "+v"(step));
   if ((int)blockIdx.x == first && threadIdx.x == 0) trust_out[s.slot[ti]] = trust;
@@ -520,6 +599,114 @@ __global__ __launch_bounds__(256) void mt_lars_update_kernel(
   const long long o = a.off[ti] + j;
   master_update4<SgdRule>(reinterpret_cast<const uint16_t*>(a.ptr[ti]) + j, master + o, mom + o,
                           nullptr, wbf + o, step, h);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sharded LARS (ShardedMasterSGD rule="lars"): a rank's shard of a reduce-scattered sub-range
+// intersects several tensors; each intersection is a PIECE of the walk above (a.ptr[i]: its summed
+// gradient inside the shard, bf16 or, WIDE, fp32; a.off[i] / a.n[i]: its fp32 masters; s.slot[i]:
+// its tensor's index in the sub-range). The norms are those of the averaged gradient d = g * scale
+// (an fp32 product), summed over ALL ranks' pieces of a tensor, so the step is three parts:
+//   shard_lars_part_kernel  mt_lars_norms_kernel over pieces: part[chunk] = (sum w^2, sum d^2)
+//   shard_lars_sums_kernel  one block per piece: its partials in fp64 (block_sum_pairs' fixed
+//                           order) to sums[2 * slot], sums[2 * slot + 1]
+//   -- the host all-reduces sums (fp64, SUM): every rank then holds the same bits --
+//   shard_lars_trust_kernel trust[slot] for every tensor of the sub-range, from the reduced sums
+//   shard_lars_update_kernel every block forms its piece's trust the same way and applies
+//                           SgdScaledRule with step = lr * trust
+// Slots without a piece on this rank hold 0.0: f64_zero_kernel writes all of sums first. No
+// atomics; the same bits on every run.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void f64_zero_kernel(double* __restrict__ v, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) v[i] = 0.0;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void shard_lars_part_kernel(MtArgs a, int part_base,
+                                                              const float* __restrict__ master,
+                                                              float scale,
+                                                              float2* __restrict__ part) {
+  // one wave per 1024-element chunk, as mt_lars_norms_kernel: no LDS, no barrier
+  const int chunk = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (chunk >= a.blk_begin[a.count]) return;
+  long long j0;
+  const int ti = mt_chunk(a, chunk, j0);
+  j0 += (threadIdx.x & 63) * 4;
+  const long long n = a.n[ti];
+  const float* wp = master + a.off[ti];
+  float4 g4[4], w4[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // n % 4 == 0 (host-checked): 4 whole elements or none
+    const long long j = j0 + k * 256;
+    const bool live = j < n;
+    g4[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+      if constexpr (WIDE) {
+        g4[k] = *reinterpret_cast<const float4*>(a.ptr[ti] + j);
+      } else {
+        const uint16_t* gp = reinterpret_cast<const uint16_t*>(a.ptr[ti]);
+        bf16x4_unpack(*reinterpret_cast<const uint2*>(gp + j), &g4[k].x);
+      }
+    }
+    w4[k] = live ? *reinterpret_cast<const float4*>(wp + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float sw = 0.f, sg = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float* g = &g4[k].x;
+    const float* w = &w4[k].x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = g[e] * scale;
+      sw += w[e] * w[e];
+      sg += d * d;
+    }
+  }
+  sw = wave_sum(sw);
+  sg = wave_sum(sg);
+  if ((threadIdx.x & 63) == 0) part[part_base + chunk] = make_float2(sw, sg);
+}
+
+__global__ __launch_bounds__(256) void shard_lars_sums_kernel(MtArgs a, LarsSlots s,
+                                                              const float2* __restrict__ part,
+                                                              double* __restrict__ sums) {
+  __shared__ double red[8];
+  const int ti = blockIdx.x;  // one block per piece
+  const int first = a.blk_begin[ti];
+  double sw, sg;
+  block_sum_pairs(part + s.part_base + first, a.blk_begin[ti + 1] - first, red, sw, sg);
+  if (threadIdx.x == 0) {
+    sums[2 * s.slot[ti]] = sw;
+    sums[2 * s.slot[ti] + 1] = sg;
+  }
+}
+
+__global__ __launch_bounds__(256) void shard_lars_trust_kernel(const double* __restrict__ sums,
+                                                               float* __restrict__ trust,
+                                                               int n_slots, ArenaOptHyper h) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_slots)
+    trust[i] = lars_trust((float)sqrt(sums[2 * i]), (float)sqrt(sums[2 * i + 1]), h);
+}
+
+// h: lr / lr_ptr, b = momentum, wd, a = eeta, eps, scale (ArenaOptHyper's LARS column + scale).
+template <bool WIDE>
+__global__ __launch_bounds__(256) void shard_lars_update_kernel(
+    MtArgs a, LarsSlots s, float* __restrict__ master, float* __restrict__ mom,
+    uint16_t* __restrict__ wbf, const double* __restrict__ sums, ArenaOptHyper h) {
+  const float lr = opt_step_size<SgdScaledRule>(h);
+  long long j;
+  const int ti = mt_chunk(a, (int)blockIdx.x, j);
+  j += threadIdx.x * 4;
+  const int slot = s.slot[ti];
+  const float trust = lars_trust((float)sqrt(sums[2 * slot]), (float)sqrt(sums[2 * slot + 1]), h);
+  float step = lr * trust;
+  asm volatile("" : "+v"(step));
+  if (j >= a.n[ti]) return;  // n % 4 == 0 (host-checked): a live thread owns 4 whole elements
+  const long long o = a.off[ti] + j;
+  shard_update4<SgdScaledRule, WIDE ? SHARD_WIDE : SHARD_MASTER>(a.ptr[ti], j, master + o, mom + o,
+                                                                 nullptr, wbf + o, step, h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -590,6 +777,42 @@ hipError_t launch_f32(const float* const* grads, const long long* offs, const lo
 inline bool rule_args_ok(int rule, const float* st0, const float* st1, const ArenaOptHyper& h) {
   if (rule != ARENA_OPT_SGD && rule != ARENA_OPT_RMSPROP && rule != ARENA_OPT_ADAM) return false;
   return st0 && (rule == ARENA_OPT_SGD || st1) && (rule != ARENA_OPT_ADAM || h.corr);
+}
+
+template <class RULE>
+hipError_t launch_shard(const void* grad, int grad_bf16, float* w32, float* st0, float* st1,
+                        void* wbf, long long n, const ArenaOptHyper& h, hipStream_t stream) {
+  const dim3 grid((unsigned)std::min<long long>((n + 1023) / 1024, 4096)), block(256);
+  uint16_t* wb = reinterpret_cast<uint16_t*>(wbf);
+  if (grad_bf16)
+    hipLaunchKernelGGL((shard_update_kernel<RULE, SHARD_MASTER>), grid, block, 0, stream, grad, w32,
+                       st0, st1, wb, n, h);
+  else if (wbf)
+    hipLaunchKernelGGL((shard_update_kernel<RULE, SHARD_WIDE>), grid, block, 0, stream, grad, w32,
+                       st0, st1, wb, n, h);
+  else
+    hipLaunchKernelGGL((shard_update_kernel<RULE, SHARD_F32>), grid, block, 0, stream, grad, w32,
+                       st0, st1, wb, n, h);
+  return hipGetLastError();
+}
+
+// The pieces of a shard as the multi-tensor walk takes them: piece i's gradient pointer.
+std::vector<const void*> piece_grads(const void* grad, int grad_bf16, const long long* goffs,
+                                     int count) {
+  std::vector<const void*> ptrs(count);
+  for (int i = 0; i < count; ++i)
+    ptrs[i] = reinterpret_cast<const char*>(grad) + goffs[i] * (grad_bf16 ? 2 : 4);
+  return ptrs;
+}
+
+bool pieces_ok(const long long* goffs, const long long* moffs, const long long* ns,
+               const int* slots, int count, int n_slots) {
+  if (count < 0 || n_slots < 0 || !mt_segments_ok(goffs, ns, count, 4) ||
+      !mt_segments_ok(moffs, ns, count, 4))
+    return false;
+  for (int i = 0; i < count; ++i)
+    if (slots[i] < 0 || slots[i] >= n_slots) return false;
+  return true;
 }
 
 }  // namespace
@@ -674,6 +897,99 @@ hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* m
     hipLaunchKernelGGL(shard_sgd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, stream, grad,
                        w32, mom, nullptr, n, lr, lr_ptr, mu, wd, scale);
   return hipGetLastError();
+}
+
+// `rule` over one flat range (a rank's shard of a reduce-scattered bucket), n % 4 == 0:
+//   grad_bf16, wbf:   bf16 gradient, fp32 master w32 and states, rounded bf16 weights to wbf
+//   fp32 grad, !wbf:  the fp32 weights w32 are their own masters
+//   fp32 grad, wbf:   the wide layout: fp32 gradient, fp32 master and states, bf16 weights to wbf
+// RMSProp and Adam (st1, Adam: hyper.corr) in all three; SGD (SgdScaledRule) in the wide layout
+// only: the other two are arena_shard_sgd's, whose bits must not move.
+hipError_t arena_shard_update(int rule, const void* grad, int grad_bf16, float* w32, float* st0,
+                              float* st1, void* wbf, long long n, ArenaOptHyper hyper,
+                              hipStream_t stream) {
+  if (!grad || !w32 || n < 0 || n % 4 || (grad_bf16 && !wbf) ||
+      !rule_args_ok(rule, st0, st1, hyper) || (rule == ARENA_OPT_SGD && (grad_bf16 || !wbf)))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  if (rule == ARENA_OPT_SGD)
+    return launch_shard<SgdScaledRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
+  if (rule == ARENA_OPT_RMSPROP)
+    return launch_shard<RmspropRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
+  return launch_shard<AdamRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
+}
+
+// Sharded LARS, first half: sums[2 * s] / sums[2 * s + 1] = this rank's fp64 sums of w^2 / (g *
+// scale)^2 over the piece of tensor s (0.0 for the tensors without one); n_slots tensors. Piece i:
+// ns[i] elements at grad + goffs[i] and master + moffs[i] (multiples of 4), slots[i] distinct.
+// workspace: arena_mt_lars_workspace_floats(ns, count) floats, as arena_mt_lars_master's.
+hipError_t arena_shard_lars_norms(const void* grad, int grad_bf16, const long long* goffs,
+                                  const long long* moffs, const long long* ns, const int* slots,
+                                  int count, int n_slots, const float* master, float scale,
+                                  float* workspace, double* sums, hipStream_t stream) {
+  if (!sums || !pieces_ok(goffs, moffs, ns, slots, count, n_slots) ||
+      (count > 0 && (!grad || !master || !workspace)))
+    return hipErrorInvalidValue;
+  if (n_slots == 0) return hipSuccess;
+  hipLaunchKernelGGL(f64_zero_kernel, dim3((2 * n_slots + 255) / 256), dim3(256), 0, stream, sums,
+                     2 * n_slots);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const std::vector<const void*> ptrs = piece_grads(grad, grad_bf16, goffs, count);
+  float2* part = reinterpret_cast<float2*>(workspace);
+  int part_base = 0;
+  return mt_launch_groups(ptrs.data(), moffs, ns, count,
+                          [&](const MtArgs& a, int blocks, int base, int cnt) {
+    LarsSlots s;
+    for (int i = 0; i < kMtMax; ++i) s.slot[i] = i < cnt ? slots[base + i] : 0;
+    s.part_base = part_base;
+    part_base += blocks;
+    const dim3 grid((blocks + 3) / 4), block(256);
+    if (grad_bf16)
+      hipLaunchKernelGGL(shard_lars_part_kernel<false>, grid, block, 0, stream, a, s.part_base,
+                         master, scale, part);
+    else
+      hipLaunchKernelGGL(shard_lars_part_kernel<true>, grid, block, 0, stream, a, s.part_base,
+                         master, scale, part);
+    const hipError_t e2 = hipGetLastError();
+    if (e2 != hipSuccess) return e2;
+    hipLaunchKernelGGL(shard_lars_sums_kernel, dim3(cnt), block, 0, stream, a, s, part, sums);
+    return hipGetLastError();
+  });
+}
+
+// Sharded LARS, second half, after the all-reduce of sums: trust[s] for all n_slots tensors, and
+// momentum SGD (SgdScaledRule) with step lr * trust over this rank's pieces. hyper: ArenaOptHyper's
+// LARS column and scale.
+hipError_t arena_shard_lars_update(const void* grad, int grad_bf16, const long long* goffs,
+                                   const long long* moffs, const long long* ns, const int* slots,
+                                   int count, int n_slots, float* master, float* mom, void* wbf,
+                                   const double* sums, float* trust, ArenaOptHyper hyper,
+                                   hipStream_t stream) {
+  if (!trust || !sums || !(hyper.a > 0.f) || !(hyper.eps >= 0.f) ||
+      !pieces_ok(goffs, moffs, ns, slots, count, n_slots) ||
+      (count > 0 && (!grad || !master || !mom || !wbf)))
+    return hipErrorInvalidValue;
+  if (n_slots == 0) return hipSuccess;
+  hipLaunchKernelGGL(shard_lars_trust_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
+                     sums, trust, n_slots, hyper);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const std::vector<const void*> ptrs = piece_grads(grad, grad_bf16, goffs, count);
+  return mt_launch_groups(ptrs.data(), moffs, ns, count,
+                          [&](const MtArgs& a, int blocks, int base, int cnt) {
+    LarsSlots s;
+    for (int i = 0; i < kMtMax; ++i) s.slot[i] = i < cnt ? slots[base + i] : 0;
+    s.part_base = 0;
+    uint16_t* wb = reinterpret_cast<uint16_t*>(wbf);
+    if (grad_bf16)
+      hipLaunchKernelGGL(shard_lars_update_kernel<false>, dim3(blocks), dim3(256), 0, stream, a, s,
+                         master, mom, wb, sums, hyper);
+    else
+      hipLaunchKernelGGL(shard_lars_update_kernel<true>, dim3(blocks), dim3(256), 0, stream, a, s,
+                         master, mom, wb, sums, hyper);
+    return hipGetLastError();
+  });
 }
 
 hipError_t arena_lr_schedule(const long long* seg, int n_seg, long long* step, float* lr,
