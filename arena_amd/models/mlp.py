@@ -114,6 +114,11 @@ class FusedMLPTrainer:
         if batch_ahead is None:
             batch_ahead = _os.environ.get("ARENA_BATCH_AHEAD", "1") != "0"
         self.batch_ahead = bool(batch_ahead) and D <= 1024
+        # A/B knob (process-wide): ARENA_STATIC_STEP=0 keeps the run-time-shape step kernels at
+        # the workload's shape too; unset leaves the extension's switch as it is (default on)
+        if dev.type == "cuda" and _os.environ.get("ARENA_STATIC_STEP") is not None:
+            from ..ops import _ext
+            _ext.load().mlp_static_step(_os.environ["ARENA_STATIC_STEP"] != "0")
         self.xgmi = None
         if self.distributed:
             import torch.distributed as dist

@@ -257,6 +257,8 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
                                float grad_scale, ArenaCounterOp ctr, ArenaHead head,
                                hipStream_t stream);
 void arena_wgrad_short_images(int on);
+void arena_mlp_static_step(int on);
+int arena_mlp_static_step_last(int which);  // 0: forward, 1: backward; 1 = static instantiation
 hipError_t arena_softmax_xent(const float* logits, const long long* labels, int M, int C,
                               float* loss, float* dlogits, float grad_scale, hipStream_t stream);
 #ifdef ARENA_TIMELINE

@@ -2588,6 +2588,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // A/B and test switch: False keeps 128-row LDS images in the MNIST step's compiled backward
   // pair for every batch size (default True: 112 rows when the batch has at most 112)
   m.def("wgrad_short_images", [](bool on) { arena_wgrad_short_images(on ? 1 : 0); });
+  // A/B and test switch: False runs the run-time-shape step kernels at the MNIST workload's shape
+  // too (default True: the static-step instantiations where shapes, strides and alignment match)
+  m.def("mlp_static_step", [](bool on) { arena_mlp_static_step(on ? 1 : 0); });
+  // read-only: which instantiation the last mlp_fwd_logits / wgrad_grouped launch of this process
+  // was, as ("static" | "run-time", "static" | "run-time")
+  m.def("mlp_static_step_last", []() {
+    auto name = [](int w) { return arena_mlp_static_step_last(w) ? "static" : "run-time"; };
+    return py::make_tuple(name(0), name(1));
+  });
   m.def("adam_flat", &adam_flat);
   m.def("sgd_flat", &sgd_flat);
   m.def("softmax_xent", &softmax_xent);

@@ -400,6 +400,23 @@ __device__ __forceinline__ void store_u1_wt(void* p, uint32_t v) {
   asm volatile("global_store_dword %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
+// adam_apply with its fused multiply-adds spelled out. The bias update (33 of the step's 1696
+// waves, off the critical path) uses it so that its bits do not depend on how hipcc happens to
+// contract the expression in one instantiation or another: under -ffp-contract=fast the static
+// step's and the run-time kernels' bias m and v differed in the last bit. No multiply is left
+// next to an add it could be fused with; 1 - b is made opaque so that (1 - b) * g is not
+// distributed into fma(-b, g, g).
+__device__ __forceinline__ void adam_apply_fixed(const AdamCoef& c, float g, float& p, float& m,
+                                                 float& v) {
+  float omb1 = 1.0f - c.b1, omb2 = 1.0f - c.b2;
+  asm volatile("" : "+v"(omb1), "+v"(omb2));
+  g = __builtin_fmaf(g, c.gscale, c.wd * p);
+  m = __builtin_fmaf(c.b1, m, omb1 * g);
+  v = __builtin_fmaf(c.b2, v, (omb2 * g) * g);
+  const float den = __builtin_fmaf(hw_sqrt(v), c.inv_sqrt_bc2, c.eps);
+  p = __builtin_fmaf(-(c.step_size * m), hw_rcp(den), p);
+}
+
 __device__ __forceinline__ int load_label(const ArenaRowSource& lab, long long pr) {
   if (lab.dtype == 1) return (int)static_cast<const uint8_t*>(lab.ptr)[pr];
   if (lab.dtype == 2) return static_cast<const int*>(lab.ptr)[pr];
@@ -919,7 +936,7 @@ __device__ __forceinline__ void wgrad_body(const WGradArgs& args, int pi, float*
       for (int r = 0; r < 4; ++r) {
         const int n = n0 + 4 * g + r;
         if (n < P.N) {
-          adam_apply(co, accb[r], pb[r], mb[r], vb[r]);
+          adam_apply_fixed(co, accb[r], pb[r], mb[r], vb[r]);
           P.pB[n] = pb[r]; P.mB[n] = mb[r]; P.vB[n] = vb[r];
         }
       }
@@ -966,6 +983,162 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   counter_op(args.ctr);  // A = B last: nothing in this kernel reads A
 }
 
+// ---------------------------------------------------------------------------------------------
+// The static step: the two step kernels compiled for ONE shape, the MNIST workload's batch 100 on
+// 784-500-10 with the batch published one step ahead. Every extent, tile count and block range is
+// a constant of the type, so the clamps, the tile-index division, the vector-path test and the
+// null-pointer selects fold, and the addresses become constant offsets off the kernel arguments.
+// The launchers pick these instantiations only when shapes, strides and alignment match exactly
+// (wgrad_step_ok / the test in arena_mlp_fwd_logits) and arena_mlp_static_step is on; tiling, K
+// split, chains, sum order, barriers, load order and the role split are those of the run-time
+// kernels, whose bodies they share.
+// ---------------------------------------------------------------------------------------------
+struct StepShape {
+  static constexpr int M = 100, K = 784, N = 500, C = 10;  // batch, input, hidden, classes
+  static constexpr int tiles_k0 = (K + 63) / 64, tiles_n0 = (N + 15) / 16;  // dW1: 13 x 32
+  static constexpr int tiles_k1 = (N + 63) / 64, tiles_n1 = (C + 15) / 16;  // dW2:  8 x 1
+  static constexpr int block_begin1 = tiles_k0 * tiles_n0;                  // 416
+  static constexpr int pub_begin = block_begin1 + tiles_k1 * tiles_n1;      // 424
+  static constexpr int pub_blocks = (M + 3) / 4;
+};
+
+// What the static backward reads, and nothing else: 336 bytes against WGradArgs' 712. A tile block
+// reads its own problem's entry of p[] and the run up to ctr_add; the publishing role's fields
+// come last. (Forcing a block's scalar loads into one batch at its entry was measured and
+// dropped: hipcc's own placement, the later fields fetched under the first vector loads, is
+// faster. docs/perf.md, "Static step".)
+struct WGradStepProb {
+  const void* x;     // layer input rows (the parity pair's base when the counter names the half)
+  float* W[3];       // Adam: P, M, V views of the weight; gradient mode: the gradient, -, -
+  float* B[3];       // the same for the bias
+  float x_scale;
+  int pad_;
+};
+struct WGradStepArgs {
+  WGradStepProb p[2];
+  const float* hd_w2; const float* hd_h;
+  float* logits2; const long long* step; const float* b2; const int* lab;
+  const float* lr_ptr; const long long* t_ptr;
+  float* loss_acc; int* correct_acc;
+  long long* ctr_dst; const long long* ctr_src;
+  float beta1, beta2, eps, wd, adam_gscale; int tf_style;
+  float grad_scale, inv_keep, loss_scale; int step_off, parity, hist_len, ctr_add;
+  // publishing role (ArenaHead::na_*; na_batch and na_K are the shape's M and K)
+  const int* na_perm; long long na_len;
+  const uint8_t* na_x; const void* na_lab; uint8_t* na_xa; int* na_ya;
+  int na_ld, na_lab_dtype;
+};
+
+template <int PI, int MODE, int SP, int MC>
+__device__ __forceinline__ void wgrad_step_tile(const WGradStepArgs& sa, const WGradStepProb& sp,
+                                                float* Xs, float* Zs, float* Ds, float* W2s,
+                                                int* Ys, float* B2s) {
+  using SH = StepShape;
+  // host-checked (wgrad_step_ok): lets the body's null-pointer selects fold
+  __builtin_assume(sa.b2 != nullptr);
+  __builtin_assume(sp.B[0] != nullptr);
+  // the run-time body's arguments, rebuilt in registers: constants from the shape, the rest from
+  // the block fetched above (the struct never exists in memory: every index into it is constant)
+  WGradArgs a{};
+  ArenaWGradProblem& P = a.p[PI];
+  P.x.ptr = sp.x;
+  P.x.dtype = PI == 0 ? 1 : 0;
+  P.x.ld = PI == 0 ? SH::K : SH::N;
+  P.x.scale = sp.x_scale;
+  P.xt = PI == 0 ? 1 : 0;
+  P.hd_mode = PI == 0 ? 2 : 1;
+  P.hd_w2 = PI == 0 ? sa.hd_w2 : nullptr;
+  P.hd_h = PI == 0 ? sa.hd_h : nullptr;
+  P.hd_inv_keep = sa.inv_keep;
+  P.M = SH::M;
+  P.K = PI == 0 ? SH::K : SH::N;
+  P.N = PI == 0 ? SH::N : SH::C;
+  P.mode = MODE;
+  if (MODE == 0) {
+    P.gW = sp.W[0]; P.gB = sp.B[0];
+  } else {
+    P.pW = sp.W[0]; P.mW = sp.W[1]; P.vW = sp.W[2];
+    P.pB = sp.B[0]; P.mB = sp.B[1]; P.vB = sp.B[2];
+  }
+  P.tiles_k = PI == 0 ? SH::tiles_k0 : SH::tiles_k1;
+  P.tiles_n = PI == 0 ? SH::tiles_n0 : SH::tiles_n1;
+  P.block_begin = PI == 0 ? 0 : SH::block_begin1;
+  a.nprob = 2;
+  a.adam.lr_ptr = sa.lr_ptr; a.adam.t_ptr = sa.t_ptr;
+  a.adam.beta1 = sa.beta1; a.adam.beta2 = sa.beta2; a.adam.eps = sa.eps;
+  a.adam.weight_decay = sa.wd; a.adam.grad_scale = sa.adam_gscale; a.adam.tf_style = sa.tf_style;
+  a.grad_scale = sa.grad_scale;
+  a.head.logits2 = sa.logits2; a.head.step = sa.step; a.head.step_off = sa.step_off;
+  a.head.parity = sa.parity; a.head.b2 = sa.b2; a.head.C = SH::C;
+  a.head.lab.ptr = sa.lab; a.head.lab.dtype = 2; a.head.lab.ld = 1;
+  a.head.loss_scale = sa.loss_scale;
+  a.head.loss_acc = sa.loss_acc; a.head.correct_acc = sa.correct_acc;
+  a.head.hist_len = sa.hist_len;
+  a.head_block = 0;
+  // parity from the counter: both halves of xa / ya hang off the pointers given
+  a.head.lab_par_stride = SP ? 0 : SH::M;
+  a.x_par_stride[PI] = (SP || PI != 0) ? 0 : SH::M * SH::K;
+  wgrad_body<10, (PI == 0 ? wgrad_spec(1, 2, 0, MODE, SP) : wgrad_spec(0, 1, 0, MODE, SP)), 0, 2,
+             MC>(a, PI, Xs, Zs, Ds, W2s, Ys, B2s);
+}
+
+// Whether a launch the host has already recognised as the fused MLP pair (published batch, no
+// gather, vectorised epilogue) is the static step exactly: shapes, row strides, both biases and
+// b2 present, the next batch published, the parity pair's strides, and the alignment the
+// staging loads of H, the X rows and the labels take for granted.
+inline bool wgrad_step_ok(const WGradArgs& a, bool sp) {
+  using SH = StepShape;
+  const ArenaWGradProblem &p0 = a.p[0], &p1 = a.p[1];
+  const ArenaHead& hd = a.head;
+  auto al = [](const void* p, uintptr_t m) { return ((uintptr_t)p & m) == 0; };
+  bool ok = p0.M == SH::M && p0.K == SH::K && p0.N == SH::N && p1.M == SH::M && p1.K == SH::N &&
+            p1.N == SH::C && hd.C == SH::C && p0.x.ld == SH::K && p1.x.ld == SH::N &&
+            hd.b2 != nullptr && hd.lab.idx == nullptr && hd.lab.dtype == 2 && hd.hist_len >= 1 &&
+            hd.na_xa != nullptr && hd.na_batch == SH::M && hd.na_K == SH::K &&
+            a.pub_begin == SH::pub_begin;
+  for (const ArenaWGradProblem* p : {&p0, &p1})
+    ok = ok && (p->mode == 1 ? p->pB != nullptr && p->mB != nullptr && p->vB != nullptr
+                             : p->gB != nullptr);
+  ok = ok && al(p0.x.ptr, 3) && al(p1.x.ptr, 15) && al(p0.hd_h, 15) && al(hd.lab.ptr, 3);
+  if (sp) ok = ok && p0.x_par_stride == 0 && p1.x_par_stride == 0 && hd.lab_par_stride == 0;
+  else ok = ok && p0.x_par_stride == SH::M * SH::K && p1.x_par_stride == 0 &&
+            hd.lab_par_stride == SH::M;
+  return ok;
+}
+
+template <int MODE, int SP, int MC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void wgrad_step_kernel(
+    WGradStepArgs sa) {
+  using SH = StepShape;
+  __shared__ __attribute__((aligned(16))) float Xs[kMC * kXsStride];
+  __shared__ __attribute__((aligned(16))) float Zs[kMC * 16];
+  __shared__ __attribute__((aligned(16))) float Ds[kMC * 16];
+  __shared__ __attribute__((aligned(16))) float W2s[16 * 16];
+  __shared__ int Ys[kMC];
+  __shared__ float B2s[16];
+  // The same order as wgrad_grouped_kernel: problem split first, the role test behind it. Neither
+  // reads a kernel argument here; the split only picks which entry of p[] is fetched
+  // (publishing blocks fetch p[1] and ignore it).
+  const int pi = (int)blockIdx.x < SH::block_begin1 ? 0 : 1;
+  int pe = pi;  // opaque, or hipcc fetches both entries and selects field by field
+  asm volatile("" : "+v"(pe));
+  const WGradStepProb sp = sa.p[__builtin_amdgcn_readfirstlane(pe)];  // (uniform again)
+  if (pi == 0) {
+    wgrad_step_tile<0, MODE, SP, MC>(sa, sp, Xs, Zs, Ds, W2s, Ys, B2s);
+  } else if ((int)blockIdx.x >= SH::pub_begin) {
+    ArenaHead hd{};
+    hd.step = sa.step; hd.step_off = sa.step_off;
+    hd.na_perm = sa.na_perm; hd.na_len = sa.na_len; hd.na_batch = SH::M;
+    hd.na_x = sa.na_x; hd.na_ld = sa.na_ld; hd.na_K = SH::K;
+    hd.na_lab = sa.na_lab; hd.na_lab_dtype = sa.na_lab_dtype;
+    hd.na_xa = sa.na_xa; hd.na_ya = sa.na_ya;
+    publish_next_batch(hd, 4 * ((int)blockIdx.x - SH::pub_begin));
+  } else {
+    wgrad_step_tile<1, MODE, SP, MC>(sa, sp, Xs, Zs, Ds, W2s, Ys, B2s);
+  }
+  counter_op(ArenaCounterOp{sa.ctr_dst, sa.ctr_src, sa.ctr_add});
+}
+
 
 // ---------------------------------------------------------------------------------------------
 // mlp_fwd_logits: linear_fwd of the hidden layer (bias, ReLU, dropout) that also emits the
@@ -979,13 +1152,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 // path reading this step's batch from xa, where the previous backward kernel published it (2: xa
 // is the half of this step's parity, chosen at launch; 3: xa is the pair, the half comes from the
 // step counter).
-template <int XT, int WAVES, int FM>
+// ST: 1 = the static step (StepShape; FM 2 / 3 only): M, N, K and C are the type's constants.
+template <int XT, int WAVES, int FM, int ST = 0>
 __global__ __launch_bounds__(WAVES * 64) void mlp_fwd_logits_kernel(
     ArenaRowSource src, const float* __restrict__ W, const float* __restrict__ bias,
-    float* __restrict__ Y, int M, int N, int K, uint32_t keep_thr, float inv_keep, uint32_t seed,
-    const long long* step_src, const float* __restrict__ W2, float* __restrict__ W2_copy, int C,
-    float* __restrict__ logits2, uint8_t* __restrict__ xb, const void* __restrict__ lab_ptr,
-    int lab_dtype, int* __restrict__ yb, ArenaCounterOp ctr, const uint8_t* __restrict__ xa) {
+    float* __restrict__ Y, int M_, int N_, int K_, uint32_t keep_thr, float inv_keep,
+    uint32_t seed, const long long* step_src, const float* __restrict__ W2,
+    float* __restrict__ W2_copy, int C_, float* __restrict__ logits2, uint8_t* __restrict__ xb,
+    const void* __restrict__ lab_ptr, int lab_dtype, int* __restrict__ yb, ArenaCounterOp ctr,
+    const uint8_t* __restrict__ xa) {
+  static_assert(ST == 0 || FM >= 2, "the static step reads the published batch");
+  const int M = ST ? StepShape::M : M_, N = ST ? StepShape::N : N_;
+  const int K = ST ? StepShape::K : K_, C = ST ? StepShape::C : C_;
   constexpr int CH = 8;
   const int lane = lane_id(), w = wave_id();
   const int g = lane >> 4, c = lane & 15;
@@ -1241,6 +1419,14 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
 // =============================================================================================
 extern "C" {
 
+// Process-wide switch for A/Bs and tests: off runs the run-time-shape kernels at every shape.
+// g_last_static: whether the last arena_mlp_fwd_logits [0] / arena_wgrad_grouped [1] launch was a
+// static-step instantiation.
+static bool g_static_step = true;
+static bool g_last_static[2] = {false, false};
+void arena_mlp_static_step(int on) { g_static_step = on != 0; }
+int arena_mlp_static_step_last(int which) { return g_last_static[which != 0] ? 1 : 0; }
+
 hipError_t arena_linear_fwd(ArenaRowSource src, const float* W, const float* bias, float* Y, int M,
                             int N, int K, int act, float keep_prob, uint32_t seed,
                             const long long* step_src, hipStream_t stream) {
@@ -1267,6 +1453,7 @@ hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float*
                                 int* yb, ArenaCounterOp ctr, const uint8_t* xa, int xa_parity,
                                 hipStream_t stream) {
   if (C < 1 || C > 16 || K % 4) return hipErrorInvalidValue;
+  g_last_static[0] = false;
   uint32_t thr = 0xFFFFFFFFu;
   float inv_keep = 1.f;
   if (keep_prob < 1.f) {
@@ -1285,7 +1472,21 @@ hipError_t arena_mlp_fwd_logits(ArenaRowSource src, const float* W, const float*
     // the batch published by the previous wgrad_grouped: xa [2][M][K] uint8, half = step parity.
     // Only the straight-line variant reads it (the binding refuses other shapes with a message).
     if (!step_fast || xa_parity < -1 || xa_parity > 1) return hipErrorInvalidValue;
-    if (xa_parity >= 0)
+    // the static step: exactly the workload's shape, a W2 snapshot asked for, and the alignment
+    // the kernel's vector loads take for granted spelled out
+    using SH = StepShape;
+    const bool stat = g_static_step && M == SH::M && N == SH::N && K == SH::K && C == SH::C &&
+                      W2_copy != nullptr && ((uintptr_t)W & 15) == 0 && ((uintptr_t)xa & 3) == 0;
+    g_last_static[0] = stat;
+    if (stat && xa_parity >= 0)
+      hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 2, 1>), grid, dim3(512), 0, stream, src, W,
+                         bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
+                         nullptr, nullptr, 0, nullptr, ctr, xa + (size_t)xa_parity * M * K);
+    else if (stat)
+      hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 3, 1>), grid, dim3(512), 0, stream, src, W,
+                         bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
+                         nullptr, nullptr, 0, nullptr, ctr, xa);
+    else if (xa_parity >= 0)
       hipLaunchKernelGGL((mlp_fwd_logits_kernel<1, 8, 2>), grid, dim3(512), 0, stream, src, W,
                          bias, Y, M, N, K, thr, inv_keep, seed, step_src, W2, W2_copy, C, logits2,
                          nullptr, nullptr, 0, nullptr, ctr, xa + (size_t)xa_parity * M * K);
@@ -1399,7 +1600,42 @@ hipError_t arena_wgrad_grouped(ArenaWGradProblem* probs, int nprob, ArenaAdam ad
                         probs[1].M <= kMC && head.lab.dtype == (g0 ? 1 : 2) &&
                         wgrad_vec_ok(probs[0]) && wgrad_vec_ok(probs[1]);
   const dim3 grid(blocks + pub_blocks), block(256);
-  if (mlp_pair) {
+  g_last_static[1] = false;
+  if (mlp_pair && g_static_step && g_wgrad_short_images && !g0 && wgrad_step_ok(a, sp)) {
+    // the static step (wgrad_step_kernel): its compact argument block from the same inputs
+    WGradStepArgs sa{};
+    const int m = probs[0].mode & 1;
+    for (int i = 0; i < 2; ++i) {
+      const ArenaWGradProblem& P = a.p[i];
+      sa.p[i].x = P.x.ptr;
+      sa.p[i].x_scale = P.x.scale;
+      if (m == 0) {
+        sa.p[i].W[0] = P.gW; sa.p[i].B[0] = P.gB;
+      } else {
+        sa.p[i].W[0] = P.pW; sa.p[i].W[1] = P.mW; sa.p[i].W[2] = P.vW;
+        sa.p[i].B[0] = P.pB; sa.p[i].B[1] = P.mB; sa.p[i].B[2] = P.vB;
+      }
+    }
+    sa.hd_w2 = a.p[0].hd_w2; sa.hd_h = a.p[0].hd_h;
+    sa.logits2 = a.head.logits2; sa.step = a.head.step; sa.b2 = a.head.b2;
+    sa.lab = static_cast<const int*>(a.head.lab.ptr);
+    sa.lr_ptr = adam.lr_ptr; sa.t_ptr = adam.t_ptr;
+    sa.loss_acc = a.head.loss_acc; sa.correct_acc = a.head.correct_acc;
+    sa.ctr_dst = ctr.dst; sa.ctr_src = ctr.src;
+    sa.beta1 = adam.beta1; sa.beta2 = adam.beta2; sa.eps = adam.eps; sa.wd = adam.weight_decay;
+    sa.adam_gscale = adam.grad_scale; sa.tf_style = adam.tf_style;
+    sa.grad_scale = grad_scale; sa.inv_keep = a.p[0].hd_inv_keep;
+    sa.loss_scale = a.head.loss_scale; sa.step_off = a.head.step_off; sa.parity = a.head.parity;
+    sa.hist_len = a.head.hist_len; sa.ctr_add = ctr.add;
+    sa.na_perm = head.na_perm; sa.na_len = head.na_len; sa.na_x = head.na_x;
+    sa.na_lab = head.na_lab; sa.na_xa = head.na_xa; sa.na_ya = head.na_ya;
+    sa.na_ld = head.na_ld; sa.na_lab_dtype = head.na_lab_dtype;
+    g_last_static[1] = true;
+    if (m == 0 && sp) hipLaunchKernelGGL((wgrad_step_kernel<0, 1, kMCShort>), grid, block, 0, stream, sa);
+    else if (m == 0) hipLaunchKernelGGL((wgrad_step_kernel<0, 0, kMCShort>), grid, block, 0, stream, sa);
+    else if (sp) hipLaunchKernelGGL((wgrad_step_kernel<1, 1, kMCShort>), grid, block, 0, stream, sa);
+    else hipLaunchKernelGGL((wgrad_step_kernel<1, 0, kMCShort>), grid, block, 0, stream, sa);
+  } else if (mlp_pair) {
     const int m = probs[0].mode & 1;
     const bool short_mc = g_wgrad_short_images && probs[0].M <= kMCShort &&
                           probs[1].M <= kMCShort;
