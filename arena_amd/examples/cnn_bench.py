@@ -8,8 +8,10 @@ This is the same workload, built for MI355X:
 * ResNet v1.5 (``arena_amd.models.resnet``), NHWC (``channels_last``), bf16 autocast on the MFMA
   conv/GEMM paths, fp32 master weights;
 * momentum SGD with weight decay, as in tf_cnn_benchmarks; ``--optimizer`` selects its plain
-  SGD, RMSProp or Adam instead (TF1's forms; fused master-weight kernels on one rank), and
-  ``--lars`` scales momentum SGD's rate per weight tensor (norms reduced on the device);
+  SGD, RMSProp or Adam instead (TF1's forms; fused master-weight kernels on one rank),
+  ``--use_nesterov`` gives momentum SGD Nesterov momentum (in the same fused kernels, xGMI ones
+  included), and ``--lars`` scales momentum SGD's rate per weight tensor (norms reduced on the
+  device);
 * one process per GPU: ``hvd.DistributedOptimizer`` buckets (RCCL or the xGMI kernel on a comm
   stream) overlap the gradient allreduce with backward;
 * output lines shaped like tf_cnn_benchmarks' ``images/sec`` and ``total images/sec``;
@@ -93,6 +95,10 @@ def parse(argv=None):
                     help="tf_cnn_benchmarks' flag: momentum SGD, plain SGD (momentum 0), or TF1's "
                          "RMSProp / Adam; with master weights on one rank the fused multi-tensor "
                          "kernels inside the captured step, else plain tensor ops")
+    ap.add_argument("--use_nesterov", action="store_true",
+                    help="Nesterov momentum for --optimizer momentum (TF's MomentumOptimizer("
+                         "use_nesterov=True), torch's SGD(nesterov=True)): the step goes along "
+                         "d + momentum * m instead of m. Off by default")
     ap.add_argument("--rmsprop_decay", type=float, default=None, help="default 0.9")
     ap.add_argument("--rmsprop_momentum", type=float, default=None, help="default 0.9")
     ap.add_argument("--rmsprop_epsilon", type=float, default=None,
@@ -240,6 +246,16 @@ def parse(argv=None):
         ap.error("--lars_eeta must be > 0")
     if not args.lars_epsilon >= 0.0:
         ap.error("--lars_epsilon must be >= 0")
+    if args.use_nesterov:
+        if args.optimizer != "momentum":
+            ap.error(f"--use_nesterov needs --optimizer momentum, not {args.optimizer}")
+        if not args.momentum > 0.0:
+            ap.error("--use_nesterov needs --momentum > 0")
+        if args.lars:
+            ap.error("--use_nesterov does not apply to --lars (Nesterov momentum under LARS is "
+                     "not implemented)")
+        if args.eval:
+            ap.error("--use_nesterov does not apply to --eval (evaluation has no optimizer)")
     return args
 
 
@@ -373,6 +389,12 @@ def build(args, dev, world, segments=None):
     momentum = 0.0 if name == "sgd" else args.momentum
     lars = bool(getattr(args, "lars", False))
     rule = "lars" if lars else name if name in ("rmsprop", "adam") else "sgd"
+    nesterov = bool(getattr(args, "use_nesterov", False))
+    if nesterov and (rule != "sgd" or not momentum > 0.0):
+        raise SystemExit("--use_nesterov needs --optimizer momentum with --momentum > 0 and no "
+                         "--lars")
+    # the keyword reaches an optimizer only with the flag: without it every call is what it was
+    nest = {"nesterov": True} if nesterov else {}
     comm = getattr(args, "comm", "auto")
     bf16_gpu = dev.type == "cuda" and getattr(args, "dtype", "bf16") == "bf16"
     # --shard_optimizer: the rule runs inside ShardedMasterSGD over RCCL (opt-in; momentum SGD and
@@ -441,7 +463,7 @@ def build(args, dev, world, segments=None):
             [{"params": decay, "weight_decay": args.weight_decay},
              {"params": no_decay, "weight_decay": 0.0, "weights": "fp32"}],
             lr=lr, momentum=momentum, bucket_mb=args.bucket_mb,
-            backend=comm, order=list(model.parameters()), **hyper)
+            backend=comm, order=list(model.parameters()), **hyper, **nest)
         if hvd.rank() == 0 and opt.backend != "xgmi" and comm == "auto":
             print(f"[rank 0] ShardedMasterSGD over RCCL, {opt.backend} (ranks cannot map each "
                   "other's GPUs)", file=sys.stderr, flush=True)
@@ -455,23 +477,24 @@ def build(args, dev, world, segments=None):
         # as below, with the BN / bias group on the multi-tensor kernel that reads the device lr
         from ..ops.optim import MasterSGD, MultiTensorSGD32, OptimizerGroup
         opt = OptimizerGroup(
-            MasterSGD(decay, lr=sched, momentum=momentum, weight_decay=args.weight_decay),
-            MultiTensorSGD32(no_decay, lr=sched, momentum=momentum))
+            MasterSGD(decay, lr=sched, momentum=momentum, weight_decay=args.weight_decay, **nest),
+            MultiTensorSGD32(no_decay, lr=sched, momentum=momentum, **nest))
     elif master:
         # conv/fc weights live in bf16 (fp32 masters inside MasterSGD): no per-step casts
         from ..ops.optim import MasterSGD, OptimizerGroup
         opt = OptimizerGroup(
             MasterSGD(decay, lr=args.learning_rate, momentum=momentum,
-                      weight_decay=args.weight_decay),
+                      weight_decay=args.weight_decay, **nest),
             # BN scales / shifts and biases (fp32): torch's fused multi-tensor SGD, one launch
             # instead of the five of the foreach form
             torch.optim.SGD(no_decay, lr=args.learning_rate, momentum=momentum,
-                            fused=dev.type == "cuda", foreach=None if dev.type == "cuda" else True))
+                            fused=dev.type == "cuda", foreach=None if dev.type == "cuda" else True,
+                            **nest))
     else:
         opt = torch.optim.SGD([{"params": decay, "weight_decay": args.weight_decay},
                                {"params": no_decay, "weight_decay": 0.0}],
                               lr=args.learning_rate, momentum=momentum,
-                              foreach=dev.type == "cuda")
+                              foreach=dev.type == "cuda", **nest)
     if world > 1 and not master:
         opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
                                        bucket_mb=args.bucket_mb, comm=args.comm)
@@ -679,7 +702,7 @@ def main(argv=None) -> int:
         print(f"Model: {args.model}  Batch size: {args.batch_size} per device, "
               f"{args.batch_size * world} global  Devices: {world} x {dev.type}  "
               f"Data: {data_name}  dtype: {args.dtype}  graph: {args.graph}  comm: "
-              f"{comm_name(opt)}", flush=True)
+              f"{comm_name(opt)}{'  nesterov' if args.use_nesterov else ''}", flush=True)
     for i in range(args.num_warmup_batches):
         t = time.perf_counter()
         train_step(model, opt, x, y, amp, head=head, loader=loader, loss_sum=ep_loss,
@@ -785,6 +808,8 @@ def main(argv=None) -> int:
                    "lars": bool(args.lars),
                    "exec": "hipgraph" if graph is not None else "eager",
                    "final_loss": round(float(loss), 4)}
+            if args.use_nesterov:
+                res["nesterov"] = True
             if counts is not None:
                 res.update(accuracy_fields(counts))
             if sched is not None:

@@ -156,34 +156,55 @@ def _check_lr_t(lr_t: Optional[Tensor], like: Tensor) -> Optional[Tensor]:
 
 def mt_sgd_master(grads: Sequence[Tensor], offsets: Sequence[int], master: Tensor, mom: Tensor,
                   wbf: Tensor, *, lr: float, momentum: float, weight_decay: float,
-                  lr_t: Optional[Tensor] = None) -> None:
+                  lr_t: Optional[Tensor] = None, nesterov: bool = False) -> None:
     """One launch (per 48 tensors) of momentum SGD over bf16 grads with fp32 master weights;
     also writes the rounded bf16 weights into ``wbf`` (``mt_master_kernel<SgdRule>`` in
     ``csrc/ops/optim_kernels.hip``). ``lr_t`` (optional, fp32 [1]) is read by the kernel instead
-    of ``lr``: a schedule under graph replay."""
+    of ``lr``: a schedule under graph replay. ``nesterov``: Nesterov momentum (``NesterovRule``:
+    w -= lr * (d + momentum * mom) after the same d and mom; needs momentum > 0)."""
     _impl(master).mt_sgd_master(list(grads), [int(o) for o in offsets], master, mom, wbf,
                                 float(lr), float(momentum), float(weight_decay),
-                                lr_t=_check_lr_t(lr_t, master))
+                                lr_t=_check_lr_t(lr_t, master), **_nesterov_kw(nesterov, momentum))
+
+
+def _nesterov_kw(nesterov: bool, momentum: float) -> dict:
+    """The ``nesterov=`` keyword of the momentum-SGD updates: passed only when set, and only with
+    a momentum above 0 (:mod:`arena_amd.ops.reference` defines the rule)."""
+    if not nesterov:
+        return {}
+    if not float(momentum) > 0.0:
+        raise ValueError(f"Nesterov momentum needs momentum > 0, got {momentum}")
+    return {"nesterov": True}
 
 
 def mt_sgd_f32(grads: Sequence[Tensor], offsets: Sequence[int], w: Tensor, mom: Tensor, *,
                lr: float, momentum: float, weight_decay: float = 0.0, scale: float = 1.0,
-               lr_t: Optional[Tensor] = None) -> None:
+               lr_t: Optional[Tensor] = None, nesterov: bool = False) -> None:
     """Momentum SGD over fp32 tensors (BN scales/shifts, biases), one launch per 48 tensors:
     gradient i updates ``w`` / ``mom`` at ``[offsets[i], offsets[i] + numel_i)`` in place, any
-    sizes; d = g * scale + wd * w; mom = momentum * mom + d; w -= lr * mom."""
+    sizes; d = g * scale + wd * w; mom = momentum * mom + d; w -= lr * mom, or with ``nesterov``
+    w -= lr * (d + momentum * mom)."""
     _impl(w).mt_sgd_f32(list(grads), [int(o) for o in offsets], w, mom, float(lr), float(momentum),
-                        float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w))
+                        float(weight_decay), float(scale), lr_t=_check_lr_t(lr_t, w),
+                        **_nesterov_kw(nesterov, momentum))
 
 
 def shard_sgd(grad: Tensor, w32: Tensor, mom: Tensor, wbf: Optional[Tensor] = None, *, lr: float,
               momentum: float, weight_decay: float, scale: float,
-              lr_t: Optional[Tensor] = None) -> None:
+              lr_t: Optional[Tensor] = None, nesterov: bool = False) -> None:
     """Momentum SGD over one flat range (a rank's shard of a reduce-scattered bucket):
     d = grad * scale + wd * w32; mom = momentum * mom + d; w32 -= lr * mom; with bf16 ``grad``
     the fp32 ``w32`` are masters and ``wbf`` receives the rounded bf16 weights. An fp32 ``grad``
     with ``wbf`` is the wide layout (a reduce-scatter that summed in fp32 over fp32 masters of
-    bf16 weights), which the ``shard_update`` kernel runs."""
+    bf16 weights), which the ``shard_update`` kernel runs. ``nesterov``: w32 -= lr * (d +
+    momentum * mom); every layout then goes through ``shard_update``."""
+    if nesterov:
+        _nesterov_kw(nesterov, momentum)
+        _impl(w32).shard_update(rule=reference.OPT_NESTEROV, grad=grad, w32=w32, st0=mom, wbf=wbf,
+                                lr=float(lr), a=0.0, oma=0.0, b=float(momentum), omb=0.0, eps=0.0,
+                                weight_decay=float(weight_decay), scale=float(scale),
+                                lr_t=_check_lr_t(lr_t, w32))
+        return
     if w32.is_cuda and wbf is not None and grad.dtype == torch.float32:
         _ext.load().shard_update(rule=reference.OPT_SGD, grad=grad, w32=w32, st0=mom, wbf=wbf,
                                  lr=float(lr), a=0.0, oma=0.0, b=float(momentum), omb=0.0, eps=0.0,

@@ -359,28 +359,59 @@ class _Flat32Optimizer(_FlatOptimizer):
 _LIST_NAMES = {"momentum_buffer": "momentum buffers"}
 
 
-class MasterSGD(_MasterOptimizer):
+class _NesterovFlag:
+    """``nesterov=True`` of the momentum-SGD optimizers (:mod:`arena_amd.ops.reference` defines
+    the rule). The momentum buffer means what it means under the plain rule; a state dict carries
+    ``nesterov: True`` only with the flag, and loading a state whose flag differs raises."""
+
+    nesterov = False
+
+    def _take_nesterov(self, nesterov: bool, momentum: float) -> None:
+        self.nesterov = bool(nesterov)
+        if self.nesterov and not float(momentum) > 0.0:   # before any parameter is re-bound
+            raise ValueError(f"{type(self).__name__}(nesterov=True) needs momentum > 0, got "
+                             f"{momentum}")
+
+    def state_dict(self) -> dict:
+        state = super().state_dict()
+        if self.nesterov:
+            state["nesterov"] = True
+        return state
+
+    def load_state_dict(self, state: dict) -> None:
+        if bool(state.get("nesterov", False)) != self.nesterov:
+            raise ValueError(f"{type(self).__name__}(nesterov={self.nesterov}) cannot load a state "
+                             f"saved with nesterov={bool(state.get('nesterov', False))}")
+        super().load_state_dict(state)
+        if self.nesterov and not self.momentum > 0.0:
+            raise ValueError(f"{type(self).__name__}(nesterov=True) needs momentum > 0, the "
+                             f"loaded state has {self.momentum}")
+
+
+class MasterSGD(_NesterovFlag, _MasterOptimizer):
     """Momentum SGD (torch.optim.SGD semantics, dampening 0) with fp32 master weights.
 
     Converts every parameter in ``params`` to bf16 in place (``p.data`` becomes a view into the
     flat bf16 buffer with the parameter's own strides, so channels_last weights stay
-    channels_last). ``lr``: a float, or a :class:`DeviceLR` on the parameters' device."""
+    channels_last). ``lr``: a float, or a :class:`DeviceLR` on the parameters' device.
+    ``nesterov``: Nesterov momentum (torch's ``nesterov=True``, TF's ``use_nesterov=True``)."""
 
     _STATE = (("mom", "momentum_buffer", 0.0),)
     _HYPER = ("momentum", "weight_decay")
 
     def __init__(self, params: Iterable[Tensor], lr: Union[float, DeviceLR], momentum: float = 0.0,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, nesterov: bool = False):
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self._take_nesterov(nesterov, momentum)
         self._init_master(params, lr)
 
     def _update(self, grads, offs) -> None:
         fused.mt_sgd_master(grads, offs, self.master, self.mom, self.wbf,
                             momentum=self.momentum, weight_decay=self.weight_decay,
-                            **_lr_args(self.lr))
+                            nesterov=self.nesterov, **_lr_args(self.lr))
 
 
-class MultiTensorSGD32(_Flat32Optimizer):
+class MultiTensorSGD32(_NesterovFlag, _Flat32Optimizer):
     """Momentum SGD (torch.optim.SGD semantics, dampening 0) over fp32 parameters with fp32
     gradients, one ``mt_sgd_f32`` launch per 48 tensors: the BN / bias group next to
     :class:`MasterSGD`.
@@ -388,20 +419,23 @@ class MultiTensorSGD32(_Flat32Optimizer):
     The parameters become views into one flat fp32 buffer (16-byte aligned slots, so the kernel
     takes its vector path; values and strides unchanged), momentum lives in a second one.
     ``lr``: a float, or a :class:`DeviceLR` on the parameters' device. ``scale`` multiplies the
-    gradients (1 / world for summed gradients)."""
+    gradients (1 / world for summed gradients). ``nesterov``: Nesterov momentum, as
+    :class:`MasterSGD`'s."""
 
     _STATE = (("mom", "momentum_buffer", 0.0),)
     _HYPER = ("momentum", "weight_decay", "scale")
 
     def __init__(self, params: Iterable[Tensor], lr: Union[float, DeviceLR], momentum: float = 0.0,
-                 weight_decay: float = 0.0, scale: float = 1.0):
+                 weight_decay: float = 0.0, scale: float = 1.0, nesterov: bool = False):
         self.momentum, self.weight_decay = float(momentum), float(weight_decay)
         self.scale = float(scale)
+        self._take_nesterov(nesterov, momentum)
         self._init_flat32(params, lr)
 
     def _update(self, grads, offs) -> None:
         fused.mt_sgd_f32(grads, offs, self.w, self.mom, momentum=self.momentum,
-                         weight_decay=self.weight_decay, scale=self.scale, **_lr_args(self.lr))
+                         weight_decay=self.weight_decay, scale=self.scale,
+                         nesterov=self.nesterov, **_lr_args(self.lr))
 
 
 # ---------------------------------------------------------------------------------------- LARS

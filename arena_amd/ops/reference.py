@@ -291,22 +291,30 @@ def _lr_value(lr, lr_t):
     return float(lr_t.reshape(-1)[0].item()) if lr_t is not None else lr
 
 
-def mt_sgd_master(grads, offsets, master, mom, wbf, lr, momentum, weight_decay, lr_t=None):
+def mt_sgd_master(grads, offsets, master, mom, wbf, lr, momentum, weight_decay, lr_t=None,
+                  nesterov=False):
     lr = _lr_value(lr, lr_t)
     for g, off in zip(grads, offsets):
         n = g.numel()
         w, m = master[off:off + n], mom[off:off + n]
-        m.mul_(momentum).add_(_storage_flat(g).float() + weight_decay * w)
-        w.sub_(lr * m)
+        if nesterov:
+            _nesterov(_storage_flat(g).float(), w, m, lr, momentum, weight_decay, None)
+        else:
+            m.mul_(momentum).add_(_storage_flat(g).float() + weight_decay * w)
+            w.sub_(lr * m)
         wbf[off:off + n].copy_(w)
 
 
-def mt_sgd_f32(grads, offsets, w, mom, lr, momentum, weight_decay, scale, lr_t=None):
+def mt_sgd_f32(grads, offsets, w, mom, lr, momentum, weight_decay, scale, lr_t=None,
+               nesterov=False):
     """CPU reference of the HIP ``mt_sgd_f32`` kernel (same operation order as ``shard_sgd``)."""
     lr = _lr_value(lr, lr_t)
     for g, off in zip(grads, offsets):
         n = g.numel()
         ws, m = w[off:off + n], mom[off:off + n]
+        if nesterov:
+            _nesterov(_storage_flat(g), ws, m, lr, momentum, weight_decay, scale)
+            continue
         d = _storage_flat(g) * scale + weight_decay * ws
         m.mul_(momentum).add_(d)
         ws.sub_(lr * m)
@@ -375,6 +383,30 @@ def _adam(g, w, m, v, step, b1, omb1, b2, omb2, eps, wd, scale):
     m.copy_(_f32(b1) * m + _f32(omb1) * d)
     v.copy_(_f32(b2) * v + _f32(omb2) * (d * d))
     w.sub_(step * m / (torch.sqrt(v) + _f32(eps)))
+
+
+# ------------------------------------------------------------------------------------------------
+# Nesterov momentum: TF's ``MomentumOptimizer(use_nesterov=True)`` (what tf_cnn_benchmarks'
+# ``--optimizer momentum`` builds), which is also ``torch.optim.SGD(nesterov=True)`` with dampening
+# 0. Defined once, here; the HIP kernels (``NesterovRule`` / ``NesterovScaledRule`` in
+# csrc/ops/optim_kernels.hip, ``sgd1_nesterov`` in csrc/ccl/xgmi_ccl.hip), the optimizers'
+# ``nesterov=True`` and the tests follow it. Every operation is an fp32 operation, in the order
+# written:
+#
+#       d = g * scale + wd * w        (master layout: d = g + wd * w, no scale, as the plain rule)
+#       m = mu * m + d                (m starts at 0)
+#       w = w - step * (d + mu * m)   (step: the float lr, or the DeviceLR value)
+#
+# One state: the momentum buffer means what it means under the plain rule, so the two rules'
+# states have the same keys. The rule requires ``mu > 0``.
+# ------------------------------------------------------------------------------------------------
+def _nesterov(g, w, m, step, mu, wd, scale):
+    """One Nesterov step in place; ``scale`` None: the master layout's unscaled ``d``."""
+    if not float(mu) > 0.0:
+        raise ValueError(f"Nesterov momentum needs momentum > 0, got {mu}")
+    d = (g if scale is None else g * _f32(scale)) + _f32(wd) * w
+    m.copy_(_f32(mu) * m + d)
+    w.sub_(_f32(step) * (d + _f32(mu) * m))
 
 
 def mt_rmsprop_master(grads, offsets, master, ms, mom, wbf, lr, rho, omr, momentum, eps,
@@ -496,21 +528,23 @@ def shard_sgd(grad, w32, mom, wbf, lr, momentum, weight_decay, scale, lr_t=None)
         wbf.copy_(w32)
 
 
-OPT_SGD, OPT_RMSPROP, OPT_ADAM = 0, 1, 2      # csrc/ops/abi.h ARENA_OPT_*
+OPT_SGD, OPT_RMSPROP, OPT_ADAM, OPT_NESTEROV = 0, 1, 2, 3      # csrc/ops/abi.h ARENA_OPT_*
 
 
 def shard_update(rule, grad, w32, st0, st1=None, wbf=None, corr=None, *, lr, a, oma, b, omb, eps,
                  weight_decay, scale, lr_t=None):
     """CPU reference of the HIP ``shard_update`` kernels: ``rule`` over one flat range, ``a`` /
     ``oma`` / ``b`` / ``omb`` as ``ArenaOptHyper`` names them (RMSProp: rho, 1 - rho, momentum, -;
-    Adam: b1, 1 - b1, b2, 1 - b2; SGD: -, -, momentum, -). ``st0`` / ``st1``: RMSProp's ms / mom,
-    Adam's m / v, SGD's mom. With ``wbf`` the fp32 ``w32`` are masters and ``wbf`` receives the
-    rounded bf16 weights."""
+    Adam: b1, 1 - b1, b2, 1 - b2; SGD and Nesterov SGD: -, -, momentum, -). ``st0`` / ``st1``:
+    RMSProp's ms / mom, Adam's m / v, SGD's and Nesterov SGD's mom. With ``wbf`` the fp32 ``w32``
+    are masters and ``wbf`` receives the rounded bf16 weights."""
     if rule == OPT_SGD:
         shard_sgd(grad, w32, st0, wbf, lr, b, weight_decay, scale, lr_t=lr_t)
         return
     g = grad.float()
-    if rule == OPT_RMSPROP:
+    if rule == OPT_NESTEROV:
+        _nesterov(g, w32, st0, _lr_value(lr, lr_t), b, weight_decay, scale)
+    elif rule == OPT_RMSPROP:
         _rmsprop(g, w32, st0, st1, _lr_value(lr, lr_t), a, oma, b, eps, weight_decay, scale)
     elif rule == OPT_ADAM:
         step = _f32(_lr_value(lr, lr_t)) * corr.reshape(())

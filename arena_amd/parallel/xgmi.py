@@ -350,6 +350,8 @@ class XgmiComm:
             run("adam", self._selftest_adam)
             run("sgd_bf16", self._selftest_sgd_bf16)
             run("sgd_f32", self._selftest_sgd_f32)
+            run("sgd_bf16_nesterov", lambda: self._selftest_sgd_bf16(nesterov=True))
+            run("sgd_f32_nesterov", lambda: self._selftest_sgd_f32(nesterov=True))
         if int(self._err.item()):
             res["timeout"] = "a barrier wait timed out during the self-test"
             self._err.zero_()
@@ -388,7 +390,15 @@ class XgmiComm:
                 return False
         return True
 
-    def _selftest_sgd_bf16(self) -> bool:
+    @staticmethod
+    def _sgd_ref(w, m, g, lr, mu, wd, nesterov):
+        """One reference step of the sharded SGD kernels (power-of-two coefficients: exact
+        products, so any contraction gives these bits); ``nesterov``: steps along d + mu * m."""
+        d = g + wd * w
+        m = mu * m + d
+        return w - lr * ((d + mu * m) if nesterov else m), m
+
+    def _selftest_sgd_bf16(self, nesterov: bool = False) -> bool:
         bf = torch.bfloat16
         words = min(self.staging_elems, self.param_elems)
         off = 8 * 3                                      # a bucket that does not start at 0
@@ -405,27 +415,27 @@ class XgmiComm:
         ref_w, ref_m = w0.clone(), torch.zeros(n, device="cuda")
         lr, mu, wd = 2.0 ** -4, 0.5, 2.0 ** -10
         lr_t = torch.full((1,), lr, device="cuda")
+        kw = {"nesterov": True} if nesterov else {}
         for step in range(3):                            # the last one in the lr_ptr form
             g = self._grad_rows(n, step, 0.25)
             stage[off:off + n].copy_(g[self.rank].to(bf))
             gsum = g[0].clone()
             for x in g[1:]:
                 gsum += x
-            ref_m = mu * ref_m + (gsum + wd * ref_w)
-            ref_w = ref_w - lr * ref_m
+            ref_w, ref_m = self._sgd_ref(ref_w, ref_m, gsum, lr, mu, wd, nesterov)
             self._prewarm()
             self._gate()
             if step < 2:
-                self.peers.sgd_bf16(master, mom, off, n, lr, mu, wd, 1.0)
+                self.peers.sgd_bf16(master, mom, off, n, lr, mu, wd, 1.0, **kw)
             else:   # a kernel that ignored lr_ptr would step with lr 0 and mismatch
-                self.peers.sgd_bf16(master, mom, off, n, 0.0, mu, wd, 1.0, lr_t)
+                self.peers.sgd_bf16(master, mom, off, n, 0.0, mu, wd, 1.0, lr_t, **kw)
             torch.cuda.synchronize()
             if not torch.equal(wbf[off:off + n], ref_w.to(bf)):
                 return False
         lo, hi = self.ext.ccl_sgd_shard(off, n, self.world, self.rank)
         return bool(torch.equal(master[lo:hi], ref_w[lo - off:hi - off]))
 
-    def _selftest_sgd_f32(self) -> bool:
+    def _selftest_sgd_f32(self, nesterov: bool = False) -> bool:
         words = min(self.staging_elems, self.param_elems)
         off = 4 * 5
         n = (min(words - off, 1 << 16) // 4) * 4
@@ -437,20 +447,20 @@ class XgmiComm:
         ref_w, ref_m = w0.clone(), torch.zeros(n, device="cuda")
         lr, mu, wd = 2.0 ** -4, 0.5, 2.0 ** -10
         lr_t = torch.full((1,), lr, device="cuda")
+        kw = {"nesterov": True} if nesterov else {}
         for step in range(3):                            # the last one in the lr_ptr form
             g = self._grad_rows(n, step, 0.25)
             self._buf[off:off + n].copy_(g[self.rank])
             gsum = g[0].clone()
             for x in g[1:]:
                 gsum += x
-            ref_m = mu * ref_m + (gsum + wd * ref_w)
-            ref_w = ref_w - lr * ref_m
+            ref_w, ref_m = self._sgd_ref(ref_w, ref_m, gsum, lr, mu, wd, nesterov)
             self._prewarm()
             self._gate()
             if step < 2:
-                self.peers.sgd_f32(mom, off, n, lr, mu, wd, 1.0)
+                self.peers.sgd_f32(mom, off, n, lr, mu, wd, 1.0, **kw)
             else:
-                self.peers.sgd_f32(mom, off, n, 0.0, mu, wd, 1.0, lr_t)
+                self.peers.sgd_f32(mom, off, n, 0.0, mu, wd, 1.0, lr_t, **kw)
             torch.cuda.synchronize()
             if not torch.equal(self._buf2[off:off + n], ref_w):
                 return False

@@ -77,6 +77,12 @@ construction; nothing in a step reads a device value on the host. The xGMI kerne
 SGD only: ``backend="xgmi"`` refuses the other rules and ``"auto"`` then skips it. A bf16
 sub-range whose reduce-scatter summed in fp32 (``rccl_reduce_fp32``) is updated in the wide
 layout: fp32 gradient, fp32 master, bf16 weight out.
+
+Nesterov momentum. ``rule="sgd"`` with ``nesterov=True`` steps along ``d + momentum * m`` instead
+of ``m`` (TF's ``use_nesterov=True``, torch's ``nesterov=True`` with dampening 0;
+:mod:`arena_amd.ops.reference` defines it) on every backend: the xGMI kernels fuse it as they fuse
+the plain rule (``"auto"`` keeps choosing xGMI), and RCCL / hier run it in the ``shard_update``
+kernels in all three layouts. The momentum buffer means what it means under the plain rule.
 """
 from __future__ import annotations
 
@@ -172,7 +178,11 @@ class ShardedMasterSGD:
     group needs bf16 weights with ``numel % 4 == 0``). ``decay`` / ``eps`` / ``eeta`` may be
     overridden per group. ``state_dict`` then carries ``rule``, the second state
     (``mean_square`` / ``exp_avg_sq``; ``momentum_buffer`` holds RMSProp's momentum and Adam's
-    first moment) and the clock; loading another rule's state raises."""
+    first moment) and the clock; loading another rule's state raises.
+
+    ``nesterov``: Nesterov momentum for ``rule="sgd"`` (every backend; ``momentum`` > 0, in every
+    param group). ``state_dict`` then carries ``nesterov: True``; loading a state whose flag
+    differs raises. The other rules refuse it."""
 
     def __init__(self, params: Iterable, lr, momentum: float = 0.0,
                  weight_decay: float = 0.0, bucket_mb: float = 16.0, group=None,
@@ -181,9 +191,13 @@ class ShardedMasterSGD:
                  rccl_reduce_fp32: Optional[bool] = None, local_size: Optional[int] = None,
                  rule: str = "sgd", decay: float = 0.9, betas=(0.9, 0.999),
                  eps: Optional[float] = None, eeta: float = 0.001,
-                 clock: Optional[AdamClock] = None):
+                 clock: Optional[AdamClock] = None, nesterov: bool = False):
         if rule not in _RULES:
             raise ValueError(f"rule must be one of {', '.join(_RULES)} (got {rule!r})")
+        if nesterov and rule != "sgd":
+            raise ValueError(f"nesterov=True belongs to rule='sgd': rule={rule!r} has no Nesterov "
+                             "form here")
+        self.nesterov = bool(nesterov)
         if rule != "sgd" and backend == "xgmi":
             raise ValueError(f"backend='xgmi' implements momentum SGD only: rule={rule!r} is not "
                              "fused into the xGMI kernels; use backend 'rccl', 'hier' or 'auto'")
@@ -225,6 +239,9 @@ class ShardedMasterSGD:
             self.param_groups.append({"params": ps, "lr": lr_g,
                                       "momentum": float(g.get("momentum", momentum)),
                                       "weight_decay": float(g.get("weight_decay", weight_decay))})
+            if self.nesterov and not self.param_groups[-1]["momentum"] > 0.0:
+                raise ValueError("ShardedMasterSGD(nesterov=True) needs momentum > 0 (got "
+                                 f"{self.param_groups[-1]['momentum']})")
             check = {"decay": _unit_interval, "eeta": _positive,
                      "eps": _non_negative if rule == "lars" else _positive}
             for k, v in extra.items():
@@ -564,10 +581,15 @@ class ShardedMasterSGD:
     def _update_xgmi(self, r: _Range, lr, mu, wd, lr_t=None) -> None:
         if r.dtype == _BF16:
             self.comm.peers.sgd_bf16(self.master, self.mom, r.start, r.end - r.start, lr, mu, wd,
-                                     1.0 / self.world, lr_t)
+                                     1.0 / self.world, lr_t, **self._nesterov_kw())
         else:
             self.comm.peers.sgd_f32(self.mom32[r.start:r.end], self.f0 + r.start,
-                                    r.end - r.start, lr, mu, wd, 1.0 / self.world, lr_t)
+                                    r.end - r.start, lr, mu, wd, 1.0 / self.world, lr_t,
+                                    **self._nesterov_kw())
+
+    def _nesterov_kw(self) -> dict:
+        """The update kernels' ``nesterov=`` keyword, passed only with the flag."""
+        return {"nesterov": True} if self.nesterov else {}
 
     def _update_rccl(self, r: _Range, lr, mu, wd, lr_t=None) -> None:
         """reduce-scatter -> shard_sgd on the owned shard -> all-gather, on the current (comm)
@@ -590,7 +612,7 @@ class ShardedMasterSGD:
             if self.rule == "sgd":
                 fused.shard_sgd(out, self.master[lo:lo + sl], self.mom[lo:lo + sl],
                                 self.wbf[lo:lo + sl], lr=lr, momentum=mu, weight_decay=wd,
-                                scale=scale, lr_t=lr_t)
+                                scale=scale, lr_t=lr_t, **self._nesterov_kw())
             else:
                 self._shard_rule(r, out, lo, sl, lr, mu, wd, lr_t)
             self._all_gather(self.wbf, r.start, n, lo, sl)
@@ -599,7 +621,8 @@ class ShardedMasterSGD:
             self._reduce_scatter(out, self.stage32[r.start:r.end])
             if self.rule == "sgd":
                 fused.shard_sgd(out, self.w32[lo:lo + sl], self.mom32[lo:lo + sl], None, lr=lr,
-                                momentum=mu, weight_decay=wd, scale=scale, lr_t=lr_t)
+                                momentum=mu, weight_decay=wd, scale=scale, lr_t=lr_t,
+                                **self._nesterov_kw())
             else:
                 self._shard_rule(r, out, lo, sl, lr, mu, wd, lr_t)
             self._all_gather(self.w32, r.start, n, lo, sl)
@@ -799,6 +822,8 @@ class ShardedMasterSGD:
                                   for g in self.param_groups]}
         if self.rule != "sgd":
             state["rule"] = self.rule
+        if self.nesterov:
+            state["nesterov"] = True
         if self.rule in _SECOND:
             aux = self._gathered(self.aux, _BF16) if self.t16 else self.aux
             aux32 = self._gathered(self.aux32, _F32) if self.t32 else self.aux32
@@ -813,6 +838,9 @@ class ShardedMasterSGD:
         if state.get("rule", "sgd") != self.rule:
             raise ValueError(f"ShardedMasterSGD(rule={self.rule!r}) cannot load the state of "
                              f"rule {state.get('rule', 'sgd')!r}")
+        if bool(state.get("nesterov", False)) != self.nesterov:
+            raise ValueError(f"ShardedMasterSGD(nesterov={self.nesterov}) cannot load a state saved "
+                             f"with nesterov={bool(state.get('nesterov', False))}")
         masters, moms = state["master"], state["momentum_buffer"]
         seconds = state[_SECOND[self.rule]] if self.rule in _SECOND else None
         if seconds is not None and (isinstance(seconds, Tensor) or len(seconds) != len(self.params)

@@ -488,7 +488,21 @@ __device__ __forceinline__ void sgd1(const SgdCoef& c, float g, float& w, float&
   w = w - c.lr * m;
 }
 
-template <int W>
+// Nesterov momentum (arena_amd/ops/reference.py defines it; NesterovScaledRule in
+// csrc/ops/optim_kernels.hip): the same d and m, the step along d + mu * m.
+__device__ __forceinline__ void sgd1_nesterov(const SgdCoef& c, float g, float& w, float& m) {
+  const float d = g * c.scale + c.wd * w;
+  m = c.mu * m + d;
+  w = w - c.lr * (d + c.mu * m);
+}
+
+template <bool NESTEROV>
+__device__ __forceinline__ void sgd_step(const SgdCoef& c, float g, float& w, float& m) {
+  if constexpr (NESTEROV) sgd1_nesterov(c, g, w, m);
+  else sgd1(c, g, w, m);
+}
+
+template <int W, bool NESTEROV>
 __global__ __launch_bounds__(kThreads) void xgmi_sgd_bf16_kernel(ArenaXgmiPeers P,
                                                                   float* __restrict__ master,
                                                                   float* __restrict__ mom,
@@ -543,7 +557,7 @@ __global__ __launch_bounds__(kThreads) void xgmi_sgd_bf16_kernel(ArenaXgmiPeers 
       float* wv = &w[u][0].x;
       float* mv = &m[u][0].x;
 #pragma unroll
-      for (int k = 0; k < 8; ++k) sgd1(c, acc[k], wv[k], mv[k]);
+      for (int k = 0; k < 8; ++k) sgd_step<NESTEROV>(c, acc[k], wv[k], mv[k]);
       uint4 packed;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -578,7 +592,7 @@ __global__ __launch_bounds__(kThreads) void xgmi_sgd_bf16_kernel(ArenaXgmiPeers 
 // rank order), momentum SGD runs on the owned chunk of the fp32 weights -- which live in buf2 and
 // ARE the masters (no rounding on the way out) -- and the chunk is written to every rank's buf2.
 // `mom` is indexed relative to the bucket (mom[0] <-> element off). Element units are floats.
-template <int W>
+template <int W, bool NESTEROV>
 __global__ __launch_bounds__(kThreads) void xgmi_sgd_f32_kernel(ArenaXgmiPeers P,
                                                                  float* __restrict__ mom,
                                                                  long long off, long long n,
@@ -612,10 +626,10 @@ __global__ __launch_bounds__(kThreads) void xgmi_sgd_f32_kernel(ArenaXgmiPeers P
       float4 g = v[u][0];
 #pragma unroll
       for (int q = 1; q < W; ++q) g = add4(g, v[u][q]);  // fixed order: identical on every rank
-      sgd1(c, g.x, w[u].x, m[u].x);
-      sgd1(c, g.y, w[u].y, m[u].y);
-      sgd1(c, g.z, w[u].z, m[u].z);
-      sgd1(c, g.w, w[u].w, m[u].w);
+      sgd_step<NESTEROV>(c, g.x, w[u].x, m[u].x);
+      sgd_step<NESTEROV>(c, g.y, w[u].y, m[u].y);
+      sgd_step<NESTEROV>(c, g.z, w[u].z, m[u].z);
+      sgd_step<NESTEROV>(c, g.w, w[u].w, m[u].w);
       if (ok[u]) {
         st4(mom + idx[u], m[u]);
         if (P.push) {
@@ -717,6 +731,19 @@ hipError_t arena_ccl_ipc_close(void* p) { return hipIpcCloseMemHandle(p); }
     default: return hipErrorInvalidValue;                                                    \
   }
 
+// The same for a kernel template with a second, bool parameter.
+#define ARENA_CCL_DISPATCH_FLAG(W, KERNEL, FLAG, ...)                                         \
+  switch (W) {                                                                               \
+    case 2: hipLaunchKernelGGL((KERNEL<2, FLAG>), __VA_ARGS__); break;                      \
+    case 3: hipLaunchKernelGGL((KERNEL<3, FLAG>), __VA_ARGS__); break;                      \
+    case 4: hipLaunchKernelGGL((KERNEL<4, FLAG>), __VA_ARGS__); break;                      \
+    case 5: hipLaunchKernelGGL((KERNEL<5, FLAG>), __VA_ARGS__); break;                      \
+    case 6: hipLaunchKernelGGL((KERNEL<6, FLAG>), __VA_ARGS__); break;                      \
+    case 7: hipLaunchKernelGGL((KERNEL<7, FLAG>), __VA_ARGS__); break;                      \
+    case 8: hipLaunchKernelGGL((KERNEL<8, FLAG>), __VA_ARGS__); break;                      \
+    default: return hipErrorInvalidValue;                                                    \
+  }
+
 hipError_t arena_ccl_allreduce(const ArenaXgmiPeers* P, const float* in, float* out, long long n,
                                float scale, hipStream_t stream) {
   const int W = P->world;
@@ -798,20 +825,27 @@ void sgd_geometry(long long n, int W, long long* L, long long* S, int* nb) {
 
 // One bucket [off, off + n) (bf16 elements, off and n multiples of 8) of the sharded SGD: bf16
 // grads staged in every rank's buf, bf16 weights in every rank's buf2, fp32 master/mom local.
+// nesterov: Nesterov momentum (momentum > 0) instead of the plain rule.
 hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom, long long off,
                               long long n, float lr, const float* lr_ptr, float momentum, float wd,
-                              float scale, hipStream_t stream) {
+                              float scale, int nesterov, hipStream_t stream) {
   const int W = P->world;
   if (W < 2 || W > kMaxR || n <= 0 || off < 0 || n % 8 || off % 8 || P->buf2[0] == nullptr)
     return hipErrorInvalidValue;
   if ((off + n + 1) / 2 > P->buf_elems || (off + n + 1) / 2 > P->buf2_elems)
     return hipErrorInvalidValue;
+  if (nesterov && !(momentum > 0.f)) return hipErrorInvalidValue;
   long long L, S;
   int nb;
   sgd_geometry(n, W, &L, &S, &nb);
   SgdCoef c{lr, momentum, wd, scale};
-  ARENA_CCL_DISPATCH(W, xgmi_sgd_bf16_kernel, dim3(nb), dim3(kThreads), 0, stream, *P, master, mom,
-                     off, n, L, S, c, lr_ptr);
+  if (nesterov) {
+    ARENA_CCL_DISPATCH_FLAG(W, xgmi_sgd_bf16_kernel, true, dim3(nb), dim3(kThreads), 0, stream, *P,
+                            master, mom, off, n, L, S, c, lr_ptr);
+  } else {
+    ARENA_CCL_DISPATCH_FLAG(W, xgmi_sgd_bf16_kernel, false, dim3(nb), dim3(kThreads), 0, stream,
+                            *P, master, mom, off, n, L, S, c, lr_ptr);
+  }
   return hipGetLastError();
 }
 
@@ -829,17 +863,23 @@ void arena_ccl_sgd_shard(long long off, long long n, int world, int r, long long
 // every rank's buf, fp32 weights (= masters) in every rank's buf2, momentum local (bucket-relative).
 hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off, long long n,
                              float lr, const float* lr_ptr, float momentum, float wd, float scale,
-                             hipStream_t stream) {
+                             int nesterov, hipStream_t stream) {
   const int W = P->world;
   if (W < 2 || W > kMaxR || n <= 0 || off < 0 || n % 4 || off % 4 || P->buf2[0] == nullptr)
     return hipErrorInvalidValue;
   if (off + n > P->buf_elems || off + n > P->buf2_elems) return hipErrorInvalidValue;
+  if (nesterov && !(momentum > 0.f)) return hipErrorInvalidValue;
   long long L, S;
   int nb;
   geometry(n, W, &L, &S, &nb);
   SgdCoef c{lr, momentum, wd, scale};
-  ARENA_CCL_DISPATCH(W, xgmi_sgd_f32_kernel, dim3(nb), dim3(kThreads), 0, stream, *P, mom, off, n,
-                     L, S, c, lr_ptr);
+  if (nesterov) {
+    ARENA_CCL_DISPATCH_FLAG(W, xgmi_sgd_f32_kernel, true, dim3(nb), dim3(kThreads), 0, stream, *P,
+                            mom, off, n, L, S, c, lr_ptr);
+  } else {
+    ARENA_CCL_DISPATCH_FLAG(W, xgmi_sgd_f32_kernel, false, dim3(nb), dim3(kThreads), 0, stream,
+                            *P, mom, off, n, L, S, c, lr_ptr);
+  }
   return hipGetLastError();
 }
 

@@ -61,13 +61,13 @@ struct ArenaAdam {
 // The multi-tensor optimizer updates (csrc/ops/optim_kernels.hip): which rule, and its numbers.
 // RMSProp and Adam are TF1's forms (arena_amd/ops/reference.py defines them); 1 - rho / 1 - b1 /
 // 1 - b2 are formed in fp64 by the caller: the fp32 difference 1 - float(0.999) is 4.7e-5 off.
-enum { ARENA_OPT_SGD = 0, ARENA_OPT_RMSPROP = 1, ARENA_OPT_ADAM = 2 };
+enum { ARENA_OPT_SGD = 0, ARENA_OPT_RMSPROP = 1, ARENA_OPT_ADAM = 2, ARENA_OPT_NESTEROV = 3 };
 struct ArenaOptHyper {
   float lr;             // replaced by *lr_ptr when that is set
   const float* lr_ptr;  // device learning rate (DeviceLR), or null
   const float* corr;    // Adam: the clock's sqrt(1 - b2^t) / (1 - b1^t); the others: null
   float a, oma;         // RMSProp: rho, 1 - rho;  Adam: b1, 1 - b1;  LARS: eeta, unused
-  float b, omb;         // SGD, LARS, RMSProp: momentum, unused;      Adam: b2, 1 - b2
+  float b, omb;         // SGD, Nesterov, LARS, RMSProp: momentum, unused;  Adam: b2, 1 - b2
   float eps, wd;        // RMSProp, Adam, LARS: their epsilon (SGD: unused); weight decay
   float scale;          // gradient scale (fp32 layout and shard_sgd; the master layout has none)
 };
@@ -274,7 +274,8 @@ hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const 
                                int count, float* flat, float scale, int dir, hipStream_t stream);
 // Multi-tensor updates by `rule` (ARENA_OPT_*, hyper: ArenaOptHyper's column for it), one launch
 // per 48 tensors; gradient i updates [offs[i], offs[i] + ns[i]) of the flat buffers. st0 / st1: the
-// rule's fp32 state buffers (SGD keeps one: st1 is not touched).
+// rule's fp32 state buffers (SGD and Nesterov SGD keep one: st1 is not touched; Nesterov needs a
+// momentum above 0).
 //   _master: bf16 gradients, fp32 masters and states, rounded bf16 weights to wbf (offs / ns
 //            multiples of 4); no gradient scale.
 //   _f32:    fp32 tensors and gradients, any sizes and offsets.
@@ -290,8 +291,9 @@ hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* m
 // `rule` over one flat range (a data-parallel rank's shard), n % 4 == 0, pointers aligned as for
 // arena_shard_sgd, grid-stride with the same 4096-block cap. Layouts: bf16 grad + wbf (fp32 master,
 // bf16 weights written); fp32 grad without wbf (fp32 weights are their own masters); fp32 grad +
-// wbf (wide: fp32 master, bf16 weights written). RMSProp / Adam (st1; Adam: hyper.corr) in all
-// three, SGD (st1 unused) in the wide layout only; anything else is hipErrorInvalidValue.
+// wbf (wide: fp32 master, bf16 weights written). RMSProp / Adam (st1; Adam: hyper.corr) and
+// Nesterov SGD (st1 unused) in all three, SGD (st1 unused) in the wide layout only; anything else
+// is hipErrorInvalidValue.
 hipError_t arena_shard_update(int rule, const void* grad, int grad_bf16, float* w32, float* st0,
                               float* st1, void* wbf /*nullable*/, long long n, ArenaOptHyper hyper,
                               hipStream_t stream);
@@ -457,12 +459,12 @@ hipError_t arena_ccl_broadcast(const ArenaXgmiPeers* P, const float* in, float* 
 void arena_ccl_set_bcast_direct_max(long long e);
 hipError_t arena_ccl_sgd_bf16(const ArenaXgmiPeers* P, float* master, float* mom, long long off,
                               long long n, float lr, const float* lr_ptr, float momentum, float wd,
-                              float scale, hipStream_t stream);
+                              float scale, int nesterov, hipStream_t stream);
 void arena_ccl_sgd_shard(long long off, long long n, int world, int r, long long* lo,
                          long long* hi);
 hipError_t arena_ccl_sgd_f32(const ArenaXgmiPeers* P, float* mom, long long off, long long n,
                              float lr, const float* lr_ptr, float momentum, float wd, float scale,
-                             hipStream_t stream);
+                             int nesterov, hipStream_t stream);
 void arena_ccl_sgd_f32_shard(long long off, long long n, int world, int r, long long* lo,
                              long long* hi);
 hipError_t arena_ccl_allgather(const ArenaXgmiPeers* P, const float* in, float* out, long long m,

@@ -708,20 +708,23 @@ void update_f32(int rule, const MtSegments& s, Tensor& w, const ArenaOptHyper& h
 
 void mt_sgd_master(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor master,
                    Tensor mom, Tensor wbf, double lr, double momentum, double weight_decay,
-                   OptT lr_t) {
+                   OptT lr_t, bool nesterov) {
   const MtSegments s = master_segments(grads, offsets, master, {mom}, wbf, "mt_sgd_master");
   ArenaOptHyper h = opt_hyper(lr, lr_t, master, weight_decay, 1.0, "mt_sgd_master");
   h.b = (float)momentum;
-  update_master(ARENA_OPT_SGD, s, master, wbf, h, "mt_sgd_master");
+  TORCH_CHECK(!nesterov || h.b > 0.f, "mt_sgd_master: Nesterov momentum needs momentum > 0");
+  update_master(nesterov ? ARENA_OPT_NESTEROV : ARENA_OPT_SGD, s, master, wbf, h, "mt_sgd_master");
 }
 
 // Momentum SGD on fp32 tensors: gradient i updates w/mom[offsets[i], offsets[i] + numel_i).
 void mt_sgd_f32(std::vector<Tensor> grads, std::vector<int64_t> offsets, Tensor w, Tensor mom,
-                double lr, double momentum, double weight_decay, double scale, OptT lr_t) {
+                double lr, double momentum, double weight_decay, double scale, OptT lr_t,
+                bool nesterov) {
   const MtSegments s = f32_segments(grads, offsets, w, {mom}, "mt_sgd_f32");
   ArenaOptHyper h = opt_hyper(lr, lr_t, w, weight_decay, scale, "mt_sgd_f32");
   h.b = (float)momentum;
-  update_f32(ARENA_OPT_SGD, s, w, h, "mt_sgd_f32");
+  TORCH_CHECK(!nesterov || h.b > 0.f, "mt_sgd_f32: Nesterov momentum needs momentum > 0");
+  update_f32(nesterov ? ARENA_OPT_NESTEROV : ARENA_OPT_SGD, s, w, h, "mt_sgd_f32");
 }
 
 // omr / omb1 / omb2: 1 - rho / 1 - b1 / 1 - b2, formed by the caller in fp64.
@@ -900,20 +903,23 @@ void* shard_range(const Tensor& grad, const Tensor& w32, const std::vector<Tenso
 
 // The rule family over one flat range (a rank's shard), by `rule` (ARENA_OPT_*) and ArenaOptHyper's
 // column for it (a / oma / b / omb as the struct names them). SGD: the wide layout only (fp32
-// gradient with wbf); shard_sgd keeps the other two.
+// gradient with wbf); shard_sgd keeps the other two. Nesterov SGD (b: momentum > 0): all three.
 void shard_update(int64_t rule, Tensor grad, Tensor w32, Tensor st0, c10::optional<Tensor> st1,
                   c10::optional<Tensor> wbf, c10::optional<Tensor> corr, double lr, double a,
                   double oma, double b, double omb, double eps, double weight_decay, double scale,
                   OptT lr_t) {
   const char* what = "shard_update";
-  TORCH_CHECK(rule == ARENA_OPT_SGD || rule == ARENA_OPT_RMSPROP || rule == ARENA_OPT_ADAM, what,
-              ": unknown rule ", rule);
+  TORCH_CHECK(rule == ARENA_OPT_SGD || rule == ARENA_OPT_RMSPROP || rule == ARENA_OPT_ADAM ||
+                  rule == ARENA_OPT_NESTEROV,
+              what, ": unknown rule ", rule);
   std::vector<Tensor> states{st0};
   if (st1.has_value()) states.push_back(*st1);
   void* wp = shard_range(grad, w32, states, wbf, what);
   const bool bf = grad.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(rule == ARENA_OPT_SGD || st1.has_value(), what,
+  TORCH_CHECK(rule == ARENA_OPT_SGD || rule == ARENA_OPT_NESTEROV || st1.has_value(), what,
               ": RMSProp and Adam keep a second state buffer (st1)");
+  TORCH_CHECK(rule != ARENA_OPT_NESTEROV || (float)b > 0.f, what,
+              ": Nesterov momentum needs momentum (b) > 0");
   TORCH_CHECK(rule != ARENA_OPT_SGD || (!bf && wp), what,
               ": SGD runs here in the wide layout only (fp32 gradient with wbf); shard_sgd has "
               "the others");
@@ -2437,7 +2443,7 @@ class XgmiPeers {
 
   // Sharded momentum SGD over one bucket [off, off + n) of bf16 elements (see xgmi_ccl.hip).
   void sgd_bf16(Tensor master, Tensor mom, int64_t off, int64_t n, double lr, double momentum,
-                double wd, double scale, OptT lr_t) {
+                double wd, double scale, OptT lr_t, bool nesterov) {
     check_f32(master, "master");
     const float* lp = opt_lr_ptr(lr_t, master, "sgd_bf16");
     check_f32(mom, "mom");
@@ -2448,16 +2454,18 @@ class XgmiPeers {
                 "short");
     TORCH_CHECK((off + n + 1) / 2 <= p_.buf_elems && (off + n + 1) / 2 <= p_.buf2_elems,
                 "sgd_bf16: bucket exceeds the registered buffers");
+    TORCH_CHECK(!nesterov || (float)momentum > 0.f, "sgd_bf16: Nesterov momentum needs "
+                "momentum > 0");
     check_hip(arena_ccl_sgd_bf16(&p_, master.data_ptr<float>(), mom.data_ptr<float>(), off, n,
                                  (float)lr, lp, (float)momentum, (float)wd, (float)scale,
-                                 cur_stream()),
+                                 nesterov ? 1 : 0, cur_stream()),
               "xgmi_sgd_bf16");
   }
 
   // The fp32 tail bucket [off, off + n) (floats) of the same optimizer; `mom` holds the bucket's
   // momentum (bucket-relative, n floats).
   void sgd_f32(Tensor mom, int64_t off, int64_t n, double lr, double momentum, double wd,
-               double scale, OptT lr_t) {
+               double scale, OptT lr_t, bool nesterov) {
     check_f32(mom, "mom");
     const float* lp = opt_lr_ptr(lr_t, mom, "sgd_f32");
     TORCH_CHECK(p_.buf2[0] != nullptr, "sgd_f32 needs the weight buffers (buf2)");
@@ -2466,8 +2474,10 @@ class XgmiPeers {
     TORCH_CHECK(mom.numel() >= n, "sgd_f32: mom too short");
     TORCH_CHECK(off + n <= p_.buf_elems && off + n <= p_.buf2_elems,
                 "sgd_f32: bucket exceeds the registered buffers");
+    TORCH_CHECK(!nesterov || (float)momentum > 0.f, "sgd_f32: Nesterov momentum needs "
+                "momentum > 0");
     check_hip(arena_ccl_sgd_f32(&p_, mom.data_ptr<float>(), off, n, (float)lr, lp, (float)momentum,
-                                (float)wd, (float)scale, cur_stream()),
+                                (float)wd, (float)scale, nesterov ? 1 : 0, cur_stream()),
               "xgmi_sgd_f32");
   }
 
@@ -2603,10 +2613,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mt_copy_scale", &mt_copy_scale);
   m.def("mt_sgd_master", &mt_sgd_master, py::arg("grads"), py::arg("offsets"), py::arg("master"),
         py::arg("mom"), py::arg("wbf"), py::arg("lr"), py::arg("momentum"),
-        py::arg("weight_decay"), py::arg("lr_t") = py::none());
+        py::arg("weight_decay"), py::arg("lr_t") = py::none(), py::arg("nesterov") = false);
   m.def("mt_sgd_f32", &mt_sgd_f32, py::arg("grads"), py::arg("offsets"), py::arg("w"),
         py::arg("mom"), py::arg("lr"), py::arg("momentum"), py::arg("weight_decay"),
-        py::arg("scale"), py::arg("lr_t") = py::none());
+        py::arg("scale"), py::arg("lr_t") = py::none(), py::arg("nesterov") = false);
   m.def("lr_schedule", &lr_schedule);
   m.def("mt_rmsprop_master", &mt_rmsprop_master, py::arg("grads"), py::arg("offsets"),
         py::arg("master"), py::arg("ms"), py::arg("mom"), py::arg("wbf"), py::arg("lr"),
@@ -2680,10 +2690,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("allgather", &XgmiPeers::allgather)
       .def("sgd_bf16", &XgmiPeers::sgd_bf16, py::arg("master"), py::arg("mom"), py::arg("off"),
            py::arg("n"), py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("scale"),
-           py::arg("lr_t") = py::none())
+           py::arg("lr_t") = py::none(), py::arg("nesterov") = false)
       .def("sgd_f32", &XgmiPeers::sgd_f32, py::arg("mom"), py::arg("off"), py::arg("n"),
            py::arg("lr"), py::arg("momentum"), py::arg("wd"), py::arg("scale"),
-           py::arg("lr_t") = py::none())
+           py::arg("lr_t") = py::none(), py::arg("nesterov") = false)
       .def_property_readonly("world", &XgmiPeers::world)
       .def_property("push", &XgmiPeers::push, &XgmiPeers::set_push);
 #ifdef ARENA_TIMELINE

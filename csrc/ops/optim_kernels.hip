@@ -9,15 +9,17 @@
 //   mt_f32<RULE>           multi-tensor update, fp32 layout: fp32 gradients and weights, any sizes
 //   mt_lars_norms/_update  LARS over the master layout: per-tensor norms, then mt_master's SGD
 //   shard_sgd<BF16>        momentum SGD over one flat range, either layout
-//   shard_update<RULE, L>  RMSProp / Adam over one flat range in the master, fp32 or wide layout
-//                          (fp32 gradient, fp32 master, bf16 weights written); SGD in the wide one
+//   shard_update<RULE, L>  RMSProp / Adam / Nesterov SGD over one flat range in the master, fp32
+//                          or wide layout (fp32 gradient, fp32 master, bf16 weights written);
+//                          plain SGD in the wide one
 //   shard_lars_*           LARS over the pieces of a rank's shard: norms, [all-reduce], update
 //   lr_schedule, adam_tick the learning-rate schedule and Adam's bias correction, on the device
 //
 // The multi-tensor kernels share ONE walk (mt_chunk: which tensor owns this 1024-element chunk),
 // ONE 4 x bf16 pack / unpack, ONE body per layout (master_update4 / f32_update4) and ONE host
-// loop (mt_fill + mt_launch_groups); a RULE (SgdRule, SgdScaledRule, RmspropRule, AdamRule) is the
-// per-element arithmetic and the number of fp32 state buffers it keeps.
+// loop (mt_fill + mt_launch_groups); a RULE (SgdRule, SgdScaledRule, NesterovRule,
+// NesterovScaledRule, RmspropRule, AdamRule) is the per-element arithmetic and the number of fp32
+// state buffers it keeps.
 #include "common.h"
 #include "adam.h"
 
@@ -138,6 +140,10 @@ __device__ __forceinline__ uint2 bf16x4_pack(const uint32_t r[4]) {  // r: f32_t
 //   SgdScaledRule  the same with a gradient scale, in the order of the xGMI kernels' shard update
 //                  (csrc/ccl/xgmi_ccl.hip xgmi_sgd_*): d = g * scale + wd * w; m = mu * m + d;
 //                  w -= step * m. The fp32 layout and shard_sgd, both dtypes.
+//   NesterovRule / NesterovScaledRule  the two above with Nesterov momentum (TF's
+//                  use_nesterov=True, torch's nesterov=True with dampening 0;
+//                  arena_amd/ops/reference.py defines it): the same d and m, then
+//                  w = w - step * (d + mu * m). One state, which means what the plain rules' does.
 //   RmspropRule / AdamRule  TF1's forms (arena_amd/ops/reference.py defines them). Both start from
 //                  the coupled gradient d = g * scale + wd * w (scale is 1 on the master path):
 //     RMSProp (s0 = ms, s1 = mom):  ms = rho * ms + omr * (d * d)
@@ -151,6 +157,7 @@ __device__ __forceinline__ uint2 bf16x4_pack(const uint32_t r[4]) {  // r: f32_t
 // which the compiler chooses, per expression shape, which products it fuses into an FMA and which
 // it rounds on their own (g * scale + wd * w may become fma(g, scale, wd * w); g + wd * w has only
 // one product to fuse). Each rule keeps its own text; tools/optim_bits.py compares two builds' bits.
+// NesterovRule / NesterovScaledRule are two texts for the same reason.
 // ---------------------------------------------------------------------------------------------
 struct SgdRule {
   static constexpr int kStates = 1;
@@ -170,6 +177,28 @@ struct SgdScaledRule {
     const float d = g * h.scale + h.wd * w;
     m = h.b * m + d;
     w = w - step * m;
+  }
+};
+
+struct NesterovRule {
+  static constexpr int kStates = 1;
+  static constexpr bool kCorr = false;
+  static __device__ __forceinline__ void apply(float g, float& w, float& m, float&, float step,
+                                               const ArenaOptHyper& h) {
+    const float d = g + h.wd * w;
+    m = h.b * m + d;
+    w = w - step * (d + h.b * m);
+  }
+};
+
+struct NesterovScaledRule {
+  static constexpr int kStates = 1;
+  static constexpr bool kCorr = false;
+  static __device__ __forceinline__ void apply(float g, float& w, float& m, float&, float step,
+                                               const ArenaOptHyper& h) {
+    const float d = g * h.scale + h.wd * w;
+    m = h.b * m + d;
+    w = w - step * (d + h.b * m);
   }
 };
 
@@ -773,9 +802,13 @@ hipError_t launch_f32(const float* const* grads, const long long* offs, const lo
   });
 }
 
-// What a rule needs beyond its segments: its second state buffer, Adam its corr.
+// What a rule needs beyond its segments: its second state buffer, Adam its corr, Nesterov a
+// momentum above 0.
 inline bool rule_args_ok(int rule, const float* st0, const float* st1, const ArenaOptHyper& h) {
-  if (rule != ARENA_OPT_SGD && rule != ARENA_OPT_RMSPROP && rule != ARENA_OPT_ADAM) return false;
+  if (rule != ARENA_OPT_SGD && rule != ARENA_OPT_RMSPROP && rule != ARENA_OPT_ADAM &&
+      rule != ARENA_OPT_NESTEROV)
+    return false;
+  if (rule == ARENA_OPT_NESTEROV) return st0 && h.b > 0.f;
   return st0 && (rule == ARENA_OPT_SGD || st1) && (rule != ARENA_OPT_ADAM || h.corr);
 }
 
@@ -855,8 +888,8 @@ hipError_t arena_mt_copy_scale(float* const* ptrs, const long long* offs, const 
 }
 
 // Master layout. grads[i]: bf16 gradient pointers; offs/ns: segment offsets and sizes, multiples
-// of 4. st1: the rule's second state buffer (SGD: unused, may be null). hyper.scale is not read by
-// SGD and is 1 for the others on this path, whatever the caller left in it.
+// of 4. st1: the rule's second state buffer (SGD, Nesterov: unused, may be null). hyper.scale is
+// not read by SGD and Nesterov and is 1 for the others on this path, whatever the caller left in it.
 hipError_t arena_mt_update_master(int rule, const void* const* grads, const long long* offs,
                                   const long long* ns, int count, float* master, float* st0,
                                   float* st1, void* wbf, ArenaOptHyper hyper, hipStream_t stream) {
@@ -865,13 +898,16 @@ hipError_t arena_mt_update_master(int rule, const void* const* grads, const long
   hyper.scale = 1.f;
   if (rule == ARENA_OPT_SGD)
     return launch_master<SgdRule>(grads, offs, ns, count, master, st0, st1, wbf, hyper, stream);
+  if (rule == ARENA_OPT_NESTEROV)
+    return launch_master<NesterovRule>(grads, offs, ns, count, master, st0, st1, wbf, hyper, stream);
   if (rule == ARENA_OPT_RMSPROP)
     return launch_master<RmspropRule>(grads, offs, ns, count, master, st0, st1, wbf, hyper, stream);
   return launch_master<AdamRule>(grads, offs, ns, count, master, st0, st1, wbf, hyper, stream);
 }
 
 // fp32 layout. grads[i]: fp32 gradient pointers; offs/ns: segment offsets and sizes in w and the
-// state buffers (any values). SGD here is SgdScaledRule: d = g * scale + wd * w.
+// state buffers (any values). SGD here is SgdScaledRule: d = g * scale + wd * w; Nesterov is
+// NesterovScaledRule.
 hipError_t arena_mt_update_f32(int rule, const float* const* grads, const long long* offs,
                                const long long* ns, int count, float* w, float* st0, float* st1,
                                ArenaOptHyper hyper, hipStream_t stream) {
@@ -879,6 +915,8 @@ hipError_t arena_mt_update_f32(int rule, const float* const* grads, const long l
     return hipErrorInvalidValue;
   if (rule == ARENA_OPT_SGD)
     return launch_f32<SgdScaledRule>(grads, offs, ns, count, w, st0, st1, hyper, stream);
+  if (rule == ARENA_OPT_NESTEROV)
+    return launch_f32<NesterovScaledRule>(grads, offs, ns, count, w, st0, st1, hyper, stream);
   if (rule == ARENA_OPT_RMSPROP)
     return launch_f32<RmspropRule>(grads, offs, ns, count, w, st0, st1, hyper, stream);
   return launch_f32<AdamRule>(grads, offs, ns, count, w, st0, st1, hyper, stream);
@@ -903,8 +941,9 @@ hipError_t arena_shard_sgd(const void* grad, int grad_bf16, float* w32, float* m
 //   grad_bf16, wbf:   bf16 gradient, fp32 master w32 and states, rounded bf16 weights to wbf
 //   fp32 grad, !wbf:  the fp32 weights w32 are their own masters
 //   fp32 grad, wbf:   the wide layout: fp32 gradient, fp32 master and states, bf16 weights to wbf
-// RMSProp and Adam (st1, Adam: hyper.corr) in all three; SGD (SgdScaledRule) in the wide layout
-// only: the other two are arena_shard_sgd's, whose bits must not move.
+// RMSProp and Adam (st1, Adam: hyper.corr) and Nesterov SGD (NesterovScaledRule) in all three;
+// SGD (SgdScaledRule) in the wide layout only: the other two are arena_shard_sgd's, whose bits
+// must not move.
 hipError_t arena_shard_update(int rule, const void* grad, int grad_bf16, float* w32, float* st0,
                               float* st1, void* wbf, long long n, ArenaOptHyper hyper,
                               hipStream_t stream) {
@@ -914,6 +953,8 @@ hipError_t arena_shard_update(int rule, const void* grad, int grad_bf16, float* 
   if (n == 0) return hipSuccess;
   if (rule == ARENA_OPT_SGD)
     return launch_shard<SgdScaledRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
+  if (rule == ARENA_OPT_NESTEROV)
+    return launch_shard<NesterovScaledRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
   if (rule == ARENA_OPT_RMSPROP)
     return launch_shard<RmspropRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
   return launch_shard<AdamRule>(grad, grad_bf16, w32, st0, st1, wbf, n, hyper, stream);
